@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — training samples/sec of the RAT_m2 hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-cpu-baseline] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -121,7 +121,12 @@ def parse(argv=None):
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="plumbing check without a GPU: gloo process group, the host-emulation build of the kernels (tests/emu), "
                          "workload `dryrun`; the printed numbers mean nothing")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the headline region's LAST timed step returned to its caller to DIR/<name>.npy (float32): "
+                         "train_step() returns the step's total loss -> DIR/loss.npy")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # The guards of the N > 1 regions must fire BEFORE the process group's own collective timeout (= --init-timeout: RCCL's watchdog
     # aborts a rank that sits in a collective that long, SIGABRT, and the launcher then discards rank 0's line): a rank that raised
     # has left, the others wait in a collective, and only their own timer can still get the finished weak-scaling line out.
@@ -508,7 +513,7 @@ def worker(args):
     # the survivors) a watcher thread writes it out with a `terminated` note before the process ends.  SIGTERM is blocked HERE, before
     # torch (and with it every helper thread, which inherits the mask) exists, and taken with sigwait by the watcher — so that it is
     # served even while the main thread sits inside a collective or a device synchronisation.
-    last_complete = {"line": None, "why": None, "emit": None}
+    last_complete = {"line": None, "why": None, "emit": None, "dump": None}
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and int(os.environ.get("RANK", "0")) == 0:
         import signal
         import threading
@@ -521,6 +526,8 @@ def worker(args):
                     d = dict(last_complete["line"])
                     d["terminated"] = ("SIGTERM %s: a peer rank failed or the job was stopped; this is the last complete measurement"
                                        % last_complete["why"])
+                    if last_complete["dump"] is not None:
+                        last_complete["dump"]()
                     last_complete["emit"](json.dumps(d))
             finally:
                 os._exit(143)
@@ -635,6 +642,16 @@ def worker(args):
     model.graph_under_dp = graph_under_dp
     model.graph_shapes = 8                       # weak / strong / per-rank shapes and both arithmetics each get their own graph
     region_info = {}
+    snapshots = {}                               # --dump-outputs: the headline region's last timed step, by step form (graph_mode)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)          # now: a path that cannot be written fails before any measurement
+
+    def write_dump(mode):
+        """--dump-outputs: write the snapshot of step form `mode` — the form the line about to be emitted reports (rank 0)"""
+        if args.dump_outputs:
+            import numpy as np
+            for name, arr in snapshots[mode].items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
 
     def timed_region(batches, steps, warmup, label, kernel_pass=True):
         """W untimed warm-up steps, then K steps between barrier + synchronize.  The one-off host work (creating the timing
@@ -672,7 +689,7 @@ def worker(args):
         for i in range(steps):
             if args.step_times:
                 stamps.append(time.perf_counter())
-            model.train_step(batches[i % nb])
+            last = model.train_step(batches[i % nb])
             if i == 0:
                 fault("step")
                 if label == "strong" and args.fault == "%d:strong" % rank:
@@ -692,6 +709,8 @@ def worker(args):
             t = torch.tensor([elapsed], dtype=torch.float64, device=model.device if not dry else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t[0])
+        if args.dump_outputs and rank == 0 and label == ("weak" if want_weak else "strong"):     # copied now: later steps reuse the buffer
+            snapshots[graph_mode] = {"loss": last.detach().reshape(-1).to(torch.float32).cpu().numpy()}
         info = dict(graph=graph_mode, graph_prepare_steps=prep)
         if graph_mode and kernel_pass:
             model.use_graph = False
@@ -878,11 +897,12 @@ def worker(args):
                 keep = assemble(weak, None, dict(region_info), mode) if rank == 0 else None
                 if rank == 0 and last_complete["line"] is None:
                     last_complete.update(line=dict(keep, strong_scaling_error="the job ended inside the strong-scaling region"),
-                                         why="inside the strong-scaling region")
+                                         why="inside the strong-scaling region", dump=lambda: write_dump(mode))
 
                 def give_up(why):
                     if rank == 0:
                         keep["strong_scaling_error"] = why
+                        write_dump(mode)
                         emit(json.dumps(keep))
                     os._exit(0)
                 guard = threading.Timer(args.region_timeout, give_up, args=("the strong-scaling region did not finish within %.0f s" % args.region_timeout,))
@@ -914,11 +934,13 @@ def worker(args):
         info_e = dict(region_info)
         fallback = assemble(weak_e, strong_e, info_e, False) if rank == 0 else None
         if rank == 0:
-            last_complete.update(line=fallback, why="during the segmented-graph attempt (these are the eager numbers)")
+            last_complete.update(line=fallback, why="during the segmented-graph attempt (these are the eager numbers)",
+                                 dump=lambda: write_dump(False))
 
         def bail():
             if rank == 0:
                 fallback["step_mode"]["graph_attempt"] = "the segmented-graph form did not finish within %.0f s and was abandoned; these are the eager numbers" % args.graph_attempt_timeout
+                write_dump(False)
                 emit(json.dumps(fallback))
             os._exit(0)
         dog = threading.Timer(args.graph_attempt_timeout, bail)
@@ -1077,6 +1099,7 @@ def worker(args):
         if not dp and not args.no_cpu_baseline and not dry:
             result["cpu_baseline"] = cpu_baseline(args.workload, spec, args.cpu_batch or B, seed=1000, model=args.model,
                                                   timed_steps=args.cpu_steps)
+        write_dump(graph_mode)
         emit(json.dumps(result))
     if dp:
         dist.barrier()

@@ -73,7 +73,8 @@ def test_a_rank_that_fails_in_the_strong_region_does_not_cost_the_weak_scaling_l
     import time
     t0 = time.monotonic()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run-cpu", "--steps", "1", "--warmup", "1",
-                        "--fault", "1:strong", "--log-dir", str(tmp_path), "--init-timeout", "40", "--region-timeout", "600"],
+                        "--fault", "1:strong", "--log-dir", str(tmp_path), "--init-timeout", "40", "--region-timeout", "600",
+                        "--dump-outputs", str(tmp_path / "dump")],
                        capture_output=True, text=True, timeout=900, env=_clean_env())
     took = time.monotonic() - t0
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
@@ -82,6 +83,7 @@ def test_a_rank_that_fails_in_the_strong_region_does_not_cost_the_weak_scaling_l
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["value"] > 0
     assert "strong_scaling" not in out and "strong_scaling_error" in out, sorted(out)
+    assert os.listdir(str(tmp_path / "dump")) == ["loss.npy"]      # the weak region's dump goes out with its line
     assert took < 400, took
 
 
@@ -90,7 +92,7 @@ def test_a_rank_that_dies_in_the_strong_region_leaves_the_weak_scaling_line_behi
     17 — and rank 0, whose weak-scaling measurement was complete, writes that line with a `terminated` note when it is stopped (a watcher
     thread takes SIGTERM with sigwait, so it is served even while the main thread sits in a collective); the launcher relays it"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run-cpu", "--steps", "1", "--warmup", "1",
-                        "--fault", "1:strongexit", "--log-dir", str(tmp_path), "--init-timeout", "120"],
+                        "--fault", "1:strongexit", "--log-dir", str(tmp_path), "--init-timeout", "120", "--dump-outputs", str(tmp_path / "dump")],
                        capture_output=True, text=True, timeout=900, env=_clean_env())
     assert r.returncode == 17, (r.returncode, r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -98,6 +100,32 @@ def test_a_rank_that_dies_in_the_strong_region_leaves_the_weak_scaling_line_behi
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["value"] > 0 and "strong_scaling" not in out
     assert "strong_scaling_error" in out          # (+ `terminated` when the launcher's SIGTERM got there before the dead peer surfaced in a collective)
+    assert os.listdir(str(tmp_path / "dump")) == ["loss.npy"]
+
+
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: what the headline region's last timed step returned to its caller (train_step: the total loss) as float32
+    .npy.  The same arguments give the same inputs and so the same output; one more timed step (--steps) gives the next step's loss."""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
+    import build_emu
+    build_emu.build()                             # here, once: the three runs below would otherwise race to build it
+    runs = {}
+    for tag, steps in (("a", 2), ("b", 2), ("c", 3)):
+        runs[tag] = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run-cpu", "--steps", str(steps), "--warmup", "1",
+                                      "--dump-outputs", str(tmp_path / tag)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                                     env=_clean_env())
+    for tag, p in runs.items():
+        out, err = p.communicate(timeout=900)
+        assert p.returncode == 0, err[-2000:]
+        line = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == (3 if tag == "c" else 2) and line["ms_per_step"] > 0
+    import numpy as np
+    for tag in "abc":
+        assert os.listdir(str(tmp_path / tag)) == ["loss.npy"], tag
+    a, b, c = (np.load(str(tmp_path / t / "loss.npy")) for t in "abc")
+    assert a.dtype == np.float32 and a.shape == (1,) and np.isfinite(a).all()
+    np.testing.assert_allclose(a, b, rtol=1e-6, atol=0)
+    assert not np.allclose(a, c, rtol=1e-6, atol=0)
 
 
 def test_bench_launcher_deadline(tmp_path):
