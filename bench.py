@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """bench.py — training samples/sec of the RAT_m2 hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full [--no-cpu-baseline]] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 One "step" = one full training iteration of BaseModel.train_one_epoch on one synthetic batch that is already
 resident in HBM: zero_grad -> forward -> BCE(+L2) -> backward -> [all-reduce] -> clip_grad_norm(10) -> Adam.
 The timed loop rotates over NBATCH distinct batches (different ids every step).
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, --dump-outputs, the JSON line.
+`--full` adds everything else: the per-kernel / roofline / targets figures (in graph mode an eager pass of its own after the timed
+steps), and at N = 1 the exact-fp32 run, the per-rank B/8 shape, the dead-token-pruning step, the 100 M-row gather, `inference`
+and the CPU baseline (--no-extras / --no-cpu-baseline leave those out again).
 
 `--gpus N` without a torch.distributed launcher around it starts the N worker processes itself (children are spawned before
 this process touches the GPU; nothing is exec'ed) — one process per GPU, RCCL process group over 127.0.0.1.
@@ -76,7 +81,11 @@ def parse(argv=None):
     ap.add_argument("--embedding-grad", default=None, choices=["atomic", "sorted", "sparse"],
                     help="how table gradients are produced (default: the workload's / the model's `auto` rule)")
     ap.add_argument("--step-times", action="store_true", help="print the host-side issue time of every timed step to stderr")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline too: per-kernel / roofline figures (graph mode: an eager pass of their "
+                         "own), and at N = 1 the side measurements (see --no-extras) and the CPU baseline.  Off: set-up, warm-up, the timed "
+                         "steps, --dump-outputs and the line, nothing else")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="time the eager fused step instead of hipGraph replays")
     ap.add_argument("--prune", action="store_true",
                     help="time the product's default step (dead-token pruning of the last block ON) as the headline instead of the "
@@ -100,9 +109,11 @@ def parse(argv=None):
                     help="diagnostic (wide heads: heads = G x 8 at d = 64): G forward launches per layer instead of the one that loops over "
                          "the head groups (rat_attn_fwd_groups)")
     ap.add_argument("--batch", type=int, default=0, help="diagnostic: override the workload's batch size (the line then names it in config)")
-    ap.add_argument("--inference", action="store_true", help="add the `inference` object (eval forward, eager and hipGraph) even with --no-extras")
+    ap.add_argument("--inference", action="store_true",
+                    help="add the `inference` object (eval forward, eager and hipGraph) even without --full or with --no-extras")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the side measurements of the default N = 1 line (exact-fp32 run, per-rank B/8 shape, 100 M-row gather)")
+                    help="with --full: skip the side measurements of the N = 1 line (exact-fp32 run, per-rank B/8 shape, dead-token "
+                         "pruning, 100 M-row gather, inference)")
     ap.add_argument("--cpu-batch", type=int, default=0, help="batch of the CPU baseline (default 0 = the workload's own batch)")
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed steps of the CPU baseline (after 1 warm-up step)")
     ap.add_argument("--time-all-kernels", action="store_true",
@@ -660,9 +671,9 @@ def worker(args):
 
         train_step() replays a captured hipGraph from its (graph_warmup + 1)-th call of a batch shape on.  The capture has to be over
         before the LAST warm-up step; when W is too small for that, extra untimed steps are run first (`graph_prepare_steps`).  A
-        replay cannot host per-launch HIP events, so in graph mode the per-kernel numbers come from `kernel_pass`: the SAME K steps
-        once more, eagerly (same kernels, same arguments, same stream), with HIP events around every timed launch — after the
-        timed region, never inside it."""
+        replay cannot host per-launch HIP events, so in graph mode the per-kernel numbers come from `kernel_pass` (--full): the SAME
+        K steps once more, eagerly (same kernels, same arguments, same stream), with HIP events around every timed launch — after the
+        timed region, never inside it.  Without it a graph-mode region has no per-kernel numbers."""
         timer.enabled = False
         timer.reset()
         nb = len(batches)
@@ -749,9 +760,8 @@ def worker(args):
         region_info[label] = info
         return elapsed, (timer.summary(steps) if (kernel_pass or not graph_mode) else {})
 
-    def assemble(weak, strong, region_info, graph_mode):
-        primary, per_rank_batch, scaling = (weak, B, "weak") if weak is not None else (strong, B // world, "strong")
-        elapsed, ksum = primary
+    def kernel_figures(ksum, per_rank_batch):
+        """-> `roofline`, `targets`, `kernels` of the line, from a region's HIP-event records `ksum` (not empty)"""
         work = algorithmic_work(spec, per_rank_batch, args.model)
         arith = getattr(model, "arith", "f32")
         kernels = []
@@ -822,6 +832,12 @@ def worker(args):
             targets["cross_attention"] = dict(bound="mfma", what="all L=T=%d fused-attention launches of a step, fwd + bwd" % T,
                                               ms_per_step=round(cross_ms, 4), algorithmic_flop_per_step=round(cross_fl),
                                               achieved_TFLOPs=round(tf, 2), frac_of_f32_mfma_peak=round(tf / PEAK_F32_MFMA_TFLOPS, 4))
+        return dict(roofline=roofline, targets=targets, kernels=kernels)
+
+    def assemble(weak, strong, region_info, graph_mode):
+        primary, per_rank_batch, scaling = (weak, B, "weak") if weak is not None else (strong, B // world, "strong")
+        elapsed, ksum = primary
+        arith = getattr(model, "arith", "f32")
         gbatch = per_rank_batch * world
         result = dict(metric="training samples/sec at B=4096, K=10 retrieved, d=64; 1/2/4/8 MI355X",
                       value=round(gbatch * args.steps / elapsed, 1),
@@ -836,7 +852,7 @@ def worker(args):
                                   dnn=spec["dnn_hidden_units"], step="fwd+bwd+clip+adam", embedding_grad=model._grad_mode,
                                   embedding_regularizer=model._cfg["lam_emb"], sync_batch_norm=bool(dp and spec["batch_norm"]),
                                   parallelism="dp%d" % world),
-                      roofline=roofline, targets=targets, kernels=kernels)
+                      **(kernel_figures(ksum, per_rank_batch) if ksum else {}))
         if dp:
             result["world"] = dist.get_world_size()
             result["first_barrier_s"] = round(first_barrier_s, 3) if first_barrier_s is not None else None
@@ -846,11 +862,13 @@ def worker(args):
             result["strong_scaling"] = dict(value=round(B * args.steps / el, 1), unit="samples/s", ms_per_step=round(el / args.steps * 1e3, 3),
                                             global_batch=B, batch_per_gpu=B // world,
                                             partitioning="one global batch of %d samples, rank r trains on rows [r*%d, (r+1)*%d)" % (B, B // world, B // world))
+        how = ", eager launches"
+        if graph_mode:
+            how = ", replayed as a captured hipGraph" + ("; `kernels` / `roofline` / `targets` are HIP-event timings of the same K steps "
+                                                         "run eagerly right after the timed region" if ksum else "")
         result["step_mode"] = dict(region_info.get(scaling, {}),
                                    what="train_step(): fused iteration (forward, BCE, backward, [exchange], two-sweep clip+Adam with the "
-                                        "regulariser folded in)" + (", replayed as a captured hipGraph; `kernels` / `roofline` / `targets` "
-                                        "are HIP-event timings of the same K steps run eagerly right after the timed region" if graph_mode
-                                        else ", eager launches"))
+                                        "regulariser folded in)" + how)
         result["config"]["dead_token_pruning"] = bool(can_prune and model.prune_dead_tokens)
         if spec["num_heads"] > 8 and hasattr(model, "_groups_supported") and model._groups_supported():
             both = bool(model._groups_supported() & 2)
@@ -887,7 +905,7 @@ def worker(args):
         weak = strong = None
         if want_weak:                                  # every rank its own batches of B samples
             batches = [make(1000 + 16 * rank + i) for i in range(NBATCH)]
-            weak = timed_region(batches, args.steps, args.warmup, "weak")
+            weak = timed_region(batches, args.steps, args.warmup, "weak", kernel_pass=args.full)
             del batches
         if want_strong:                                # one global batch of B samples, rank r takes rows [r B/N, (r+1) B/N)
             per = B // world
@@ -909,7 +927,7 @@ def worker(args):
                 guard.daemon = True
                 guard.start()
             try:
-                strong = timed_region(batches, args.steps, max(args.warmup, 2) if weak is None else 2, "strong")
+                strong = timed_region(batches, args.steps, max(args.warmup, 2) if weak is None else 2, "strong", kernel_pass=args.full)
             except Exception as exc:                   # (this rank's error; the other ranks' watchdogs end them)
                 if guard is None:
                     raise
@@ -963,9 +981,9 @@ def worker(args):
     else:
         weak, strong = run_regions(graph_mode)
 
-    # exact-fp32 arithmetic timed beside the default one in the SAME invocation; N = 1 only
+    # --full: exact-fp32 arithmetic timed beside the default one in the SAME invocation; N = 1 only
     alt = None
-    if not dp and args.arith is None and not args.no_extras and hasattr(model, "arith_modes") and len(model.arith_modes()) > 1:
+    if args.full and not dp and args.arith is None and not args.no_extras and hasattr(model, "arith_modes") and len(model.arith_modes()) > 1:
         default_arith = model.arith
         other = [m for m in model.arith_modes() if m != default_arith][0]
         model.set_arith(other)
@@ -976,7 +994,7 @@ def worker(args):
         model.set_arith(default_arith)
         del batches
 
-    extras = not dp and not args.no_extras and not dry
+    extras = args.full and not dp and not args.no_extras and not dry
     if alt is not None and args.no_extras:
         alt = None
     # §8e's strong-scaling partitioning on ONE GPU: the per-rank shape of an 8-GPU run of the global batch (B/8 samples per step)
@@ -1096,7 +1114,7 @@ def worker(args):
         result = assemble(weak, strong, region_info, graph_mode)
         if attempts is not None:
             result["step_mode"]["attempts"] = attempts
-        if not dp and not args.no_cpu_baseline and not dry:
+        if args.full and not dp and not args.no_cpu_baseline and not dry:
             result["cpu_baseline"] = cpu_baseline(args.workload, spec, args.cpu_batch or B, seed=1000, model=args.model,
                                                   timed_steps=args.cpu_steps)
         write_dump(graph_mode)

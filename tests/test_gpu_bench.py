@@ -1,6 +1,7 @@
 """bench.py --dump-outputs on the GPU (-m gpu): in graph mode the timed steps are hipGraph replays, and the loss train_step returns is
-the graph's static output — copied after the timed region's synchronize and before the eager kernel-timing pass reuses it.  The same
-K steps run eagerly (--no-graph: no replay, no kernel pass) must return the same loss, and one more timed step must not."""
+the graph's static output — copied after the timed region's synchronize and before the eager kernel-timing pass (--full) reuses it.
+The same K steps run eagerly (--no-graph: no replay, no kernel pass) must return the same loss, and one more timed step (a plain run:
+no kernel pass, no per-kernel figures) must not."""
 import json
 import os
 import subprocess
@@ -27,10 +28,12 @@ def _bench(out_dir, *extra):
 
 
 def test_dump_of_a_graph_replay_is_the_last_timed_step(tmp_path):
-    graph, lg = _bench(tmp_path / "graph", "--steps", "3")
+    graph, lg = _bench(tmp_path / "graph", "--steps", "3", "--full")
     eager, le = _bench(tmp_path / "eager", "--steps", "3", "--no-graph")
     later, l4 = _bench(tmp_path / "later", "--steps", "4")
     assert graph["step_mode"]["graph"] is True and graph["step_mode"]["graph_prepare_steps"] == 0 and eager["step_mode"]["graph"] is False
+    assert graph["kernels"] and "eager_instrumented_ms_per_step" in graph["step_mode"]
+    assert later["step_mode"]["graph"] is True and "kernels" not in later and "eager_instrumented_ms_per_step" not in later["step_mode"]
     assert lg.dtype == np.float32 and lg.shape == (1,) and np.isfinite(lg).all()
     np.testing.assert_allclose(lg, le, rtol=2e-5, atol=0)
     assert not np.allclose(lg, l4, rtol=1e-3, atol=0)

@@ -119,9 +119,10 @@ def _bench(args, timeout=900):
 
 def test_bench_rehearsal_measures_eager_first_then_graphs_and_reports_the_exchange():
     """bench.py's N > 1 path on one RCCL rank: the eager regions are measured first, then the segmented-graph regions; the line carries
-    both attempts, the world size, the exchange form with what it put on the links and the per-phase HIP-event times"""
+    both attempts, the world size, the exchange form with what it put on the links and the per-phase HIP-event times (--full: in graph
+    form those come from the eager instrumented pass after the timed steps)"""
     import json
-    r, lines = _bench(["--dp-rehearsal", "--graph-dp", "--workload", "tiny", "--steps", "3", "--warmup", "2"])      # (--graph-dp: opt-in since round 6)
+    r, lines = _bench(["--dp-rehearsal", "--graph-dp", "--full", "--workload", "tiny", "--steps", "3", "--warmup", "2"])      # (--graph-dp: opt-in since round 6)
     if "RCCL" in r.stderr and r.returncode != 0 and "init_process_group" in r.stderr:
         pytest.skip("RCCL could not bring up a one-rank communicator here")
     assert r.returncode == 0, r.stderr[-3000:]

@@ -7,7 +7,7 @@
 #   OUT        directory under gpurun_out/ for the logs (created)
 #   --pytest   first run `python3 -m pytest ARGS` once (the parity gate of what is being measured); its tail goes to OUT/pytest.log
 #   --kbench   the measurement is `python3 tools/kbench.py ARGS`   (one kernel, stand-alone; lines matching --grep are kept)
-#   --bench    the measurement is `python3 bench.py ARGS`           (the step; the JSON line is kept and summarised at the end)
+#   --bench    the measurement is `python3 bench.py --full ARGS`    (the step; the JSON line is kept and summarised at the end)
 #   VARIANT    NAME[:ENV=VAL[,ENV=VAL...]] — NAME "hip" is the product library, any other NAME is www24-rat_amd/lib/librat_NAME.so
 #              (built by tools/variant.sh NAME file.hip -DFLAG before the call); the ENV assignments are exported for that run only
 #              (the library's knobs: RAT_ATTN_FWD_CORE=mfma32, RAT_ATTN_BWD_CORE=valu, ...)
@@ -44,7 +44,7 @@ for round in $(seq 1 "$rounds"); do
         echo "== $v (round $round)" >> "$out/ab.txt"
         timeout 900 python3 tools/kbench.py $kb 2>&1 | grep -E "$re" >> "$out/ab.txt"
       else
-        timeout 1500 python3 bench.py $be > "$out/bench_${tag}_$round.json" 2> "$out/bench_${tag}_$round.err"
+        timeout 1500 python3 bench.py --full $be > "$out/bench_${tag}_$round.json" 2> "$out/bench_${tag}_$round.err"
       fi
     )
   done

@@ -10,7 +10,7 @@ for round in 1 2; do
     lib=$PWD/www24-rat_amd/lib/librat_$v.so
     [ "$v" = "base" ] && lib=$PWD/www24-rat_amd/lib/librat_hip.so
     d=$out/${v}_r$round
-    RAT_HIP_LIBRARY=$lib rocprofv3 --kernel-trace --stats -d $d -o s --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras ${AB_BENCH_ARGS} > $d.json 2> $d.err
+    RAT_HIP_LIBRARY=$lib rocprofv3 --kernel-trace --stats -d $d -o s --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras ${AB_BENCH_ARGS} > $d.json 2> $d.err
     python3 - "$d" "$v" "$round" "$pat" <<'PY'
 import csv, glob, json, sys
 d, v, rnd, pat = sys.argv[1:5]
