@@ -53,6 +53,20 @@ typedef struct RatField {
 int rat_gather_fwd(const int32_t* idx, const int32_t* label_ids, const RatField* fields_dev, int nfields,
                    const float* label_table, float* grid, int B, int T, int L, int d, void* stream);
 
+/* rat_gather_fwd for field sets with MaskedAveragePooling sequence fields: replaces the same lines plus
+ * MaskedAveragePooling.forward (sequence.py:24-29, chosen by embedding.py:113-121).  modes_dev: device int32 [nfields],
+ * 0 = MaskedSumPooling / categorical, 1 = MaskedAveragePooling; an averaged field's grid row is, per element c,
+ * sum_i E[id_i][c] / ((float)#{i : E[id_i][c] != 0} + 1e-16f).  modes_dev = NULL is rat_gather_fwd exactly. */
+int rat_gather_fwd_pool(const int32_t* idx, const int32_t* label_ids, const RatField* fields_dev, const int32_t* modes_dev,
+                        int nfields, const float* label_table, float* grid, int B, int T, int L, int d, void* stream);
+
+/* backward of MaskedAveragePooling (autograd's DivBackward of sequence.py:27, the count a constant), run before the table-gradient
+ * stage (rat_gather_bwd or rat_sparse_reduce_grid): the rows of dgrid [B][T][S][d] of the averaged fields avg_fields_dev
+ * (device int32 [navg], field indices) and their target rows of dflat (nullable, [B][nfields*d]) are divided IN PLACE by the
+ * forward's per-element denominators, recomputed from fields_dev (the forward's tables, unchanged since the forward). */
+int rat_pool_scale_bwd(float* dgrid, float* dflat, const int32_t* idx, const RatField* fields_dev, const int32_t* avg_fields_dev,
+                       int navg, int nfields, int B, int T, int L, int d, void* stream);
+
 /* backward of the above (autograd's embedding_dense_backward + cat/stack backward, base_model.py:223).
  * dgrid [B][T][S][d]; dflat (nullable) [B][nfields*d] = gradient of the DNN branch input X_emb.flatten(1)
  * (RAT_m2.py:145-146), added onto the target rows; grad tables are ACCUMULATED into (caller zeroes them);
@@ -409,6 +423,19 @@ int rat_logit_fwd_dnn(const float* cls, int64_t cls_stride, const float* fc_w, c
                       int64_t dnn_ld, const float* dnn_w, const float* dnn_b, int dnn_k, const RatField* lr_fields_dev,
                       int nfields, const int32_t* idx, int64_t idx_stride, const float* y_true, float* y_pred,
                       float* loss_sum, int B, int d, int head, void* stream);
+/* rat_logit_fwd / rat_logit_fwd_dnn for field sets with MaskedAveragePooling fields: the LR layer's own EmbeddingLayer applies the
+ * same encoder (shallow.py:30, embedding.py:101), so an averaged field's wide term is sum_i w[id_i] / (#{w[id_i] != 0} + 1e-16f)
+ * (sequence.py:24-29).  modes_dev: device int32 [nfields] as rat_gather_fwd_pool.  lr_den (nullable): float [B][nfields] <- each
+ * (sample, field)'s denominator (1 for a summed field), what rat_logit_bwd_pool / rat_sparse_reduce_scalar_pool divide by.
+ * modes_dev = NULL and lr_den = NULL: rat_logit_fwd / rat_logit_fwd_dnn exactly. */
+int rat_logit_fwd_pool(const float* cls, int64_t cls_stride, const float* fc_w, const float* fc_b, const float* dnn_out,
+                       const RatField* lr_fields_dev, const int32_t* modes_dev, int nfields, const int32_t* idx,
+                       int64_t idx_stride, const float* y_true, float* y_pred, float* loss_sum, float* lr_den, int B, int d,
+                       int head, void* stream);
+int rat_logit_fwd_dnn_pool(const float* cls, int64_t cls_stride, const float* fc_w, const float* fc_b, const float* dnn_in,
+                           int64_t dnn_ld, const float* dnn_w, const float* dnn_b, int dnn_k, const RatField* lr_fields_dev,
+                           const int32_t* modes_dev, int nfields, const int32_t* idx, int64_t idx_stride, const float* y_true,
+                           float* y_pred, float* loss_sum, float* lr_den, int B, int d, int head, void* stream);
 /* dlogit[b] = gscale * (gscale_dev ? *gscale_dev : 1) * (y_pred - y_true)/B (x 2 for RAT_HEAD_REGRESSION) ; dcls row b (written at
  * dcls + b*dcls_stride) = dlogit*fc_w ; dfc_w, dfc_b and the LR grad tables are ACCUMULATED into (caller zeroes them).
  * gscale_dev (nullable): a DEVICE scalar — autograd's incoming loss gradient — so that backward needs no host read-back. */
@@ -421,6 +448,13 @@ int rat_logit_bwd_dnn(const float* y_pred, const float* y_true, const float* cls
                       float* dlogit, float* dcls, int64_t dcls_stride, float* dfc_w, float* dfc_b, float* ddnn_b,
                       const RatField* lr_grad_fields_dev, int nfields, const int32_t* idx, int64_t idx_stride, float gscale,
                       const float* gscale_dev, int B, int d, int head, void* stream);
+/* rat_logit_bwd / rat_logit_bwd_dnn with averaged LR fields: field f of sample b scatters dlogit[b] / lr_den[b][f] (lr_den from
+ * rat_logit_fwd_pool; a summed field's 1 leaves dlogit unchanged).  lr_den = NULL: rat_logit_bwd / rat_logit_bwd_dnn exactly;
+ * ddnn_b NULL: rat_logit_bwd's form. */
+int rat_logit_bwd_pool(const float* y_pred, const float* y_true, const float* cls, int64_t cls_stride, const float* fc_w,
+                       float* dlogit, float* dcls, int64_t dcls_stride, float* dfc_w, float* dfc_b, float* ddnn_b,
+                       const RatField* lr_grad_fields_dev, const float* lr_den, int nfields, const int32_t* idx, int64_t idx_stride,
+                       float gscale, const float* gscale_dev, int B, int d, int head, void* stream);
 
 /* ---- K1s: row-sparse / deterministic embedding gradients (BASELINE.json configs[3]; SURVEY.md §2a rows H/I, §7 hard parts 3, 7)
  * replaces, for tables too large for dense semantics, embedding_dense_backward + the dense clip/Adam pass over the tables
@@ -456,6 +490,11 @@ int rat_sparse_reduce_rows(const void* workspace, const int32_t* count_dev, cons
                            int d, int32_t* out_rows, float* out_grads, void* stream);
 int rat_sparse_reduce_scalar(const void* workspace, const int32_t* count_dev, const float* per_sample, int B, int L,
                              int32_t* out_rows, float* out_vals, float* dense_base, void* stream);
+/* rat_sparse_reduce_scalar with averaged LR fields: entry (b, column c) contributes per_sample[b] / lr_den[b][col2field_dev[c]]
+ * (lr_den [B][nfields] from rat_logit_fwd_pool).  lr_den = NULL: rat_sparse_reduce_scalar exactly. */
+int rat_sparse_reduce_scalar_pool(const void* workspace, const int32_t* count_dev, const float* per_sample, const float* lr_den,
+                                  const int32_t* col2field_dev, int nfields, int B, int L, int32_t* out_rows, float* out_vals,
+                                  float* dense_base, void* stream);
 int rat_sumsq_rows(const float* grads, const int32_t* count_dev, int64_t max_rows, int d, float* norm_sq_out, void* stream);
 int rat_adam_rows(float* w_base, float* m_base, float* v_base, const int32_t* rows, const float* grads,
                   const int32_t* count_dev, int64_t max_rows, int d, const float* norm_sq, float max_norm, float lr,

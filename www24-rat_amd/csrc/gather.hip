@@ -24,11 +24,30 @@ constexpr int GATHER_THREADS = 256;
 // 1 row the same as 2, 3 and 8 rows slower; inside the N2 training step (behind the optimizer's sweep) 85-88 us with any of them.
 constexpr int GATHER_ITEMS = RAT_GATHER_ITEMS;
 
+// MaskedAveragePooling (sequence.py:24-29): per element, the number of bag rows whose element is non-zero (-0.0 counts as zero;
+// the all-zero padding row never counts), and the true fp32 division of the sum by (count + 1e-16f).  An all-padding bag gives 0.
+struct Count4 {
+    int x, y, z, w;
+};
+
+__device__ __forceinline__ void rat_count_nonzero(Count4& cnt, const float4& w) {
+    cnt.x += w.x != 0.f ? 1 : 0; cnt.y += w.y != 0.f ? 1 : 0; cnt.z += w.z != 0.f ? 1 : 0; cnt.w += w.w != 0.f ? 1 : 0;
+}
+
+__device__ __forceinline__ void rat_divide_count(float4& v, const Count4& cnt) {
+    v.x = v.x / ((float)cnt.x + 1e-16f); v.y = v.y / ((float)cnt.y + 1e-16f);
+    v.z = v.z / ((float)cnt.z + 1e-16f); v.w = v.w / ((float)cnt.w + 1e-16f);
+}
+
 // vectorised path: d % 4 == 0, one item = one 16-byte piece of one grid row
+// AVG (a field set with MaskedAveragePooling fields; modes[f] = 1 for those): every bag also counts, per element, the rows whose
+// element is non-zero and the field's sum leaves divided by (count + 1e-16f) — sequence.py:24-29.  The count runs on the rows the
+// sum already holds in registers (no extra load); AVG = false is the sum-only instantiation, the code every existing workload runs.
+template <bool AVG>
 __global__ void __launch_bounds__(GATHER_THREADS)
 gather_fwd_vec_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict__ label_ids,
                       const RatField* __restrict__ fields, const float* __restrict__ label_table,
-                      float* __restrict__ grid, int64_t nrows, int S, int L, int d) {
+                      float* __restrict__ grid, int64_t nrows, int S, int L, int d, const int32_t* __restrict__ modes) {
     const int cpr = d >> 2;                                   // 16-byte pieces per row
     const int64_t nitems = nrows * cpr;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -38,9 +57,11 @@ gather_fwd_vec_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict
         const int32_t* idp[GATHER_ITEMS];
         const float* tab[GATHER_ITEMS];
         int vocab[GATHER_ITEMS];
+        bool avg[GATHER_ITEMS];
 #pragma unroll
         for (int u = 0; u < GATHER_ITEMS; ++u) {
             const int64_t e = e0 + (int64_t)u * stride;
+            avg[u] = false;
             src[u] = nullptr;
             extra[u] = 0;
             idp[u] = nullptr;
@@ -65,6 +86,7 @@ gather_fwd_vec_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict
                     idp[u] = ids;
                     tab[u] = f.table + piece * 4;
                     vocab[u] = f.vocab;
+                    if (AVG) avg[u] = modes[s - 1] != 0;
                 }
             }
         }
@@ -73,12 +95,16 @@ gather_fwd_vec_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict
         for (int u = 0; u < GATHER_ITEMS; ++u) v[u] = src[u] ? *src[u] : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int u = 0; u < GATHER_ITEMS; ++u) {
+            Count4 cnt{0, 0, 0, 0};
+            if (AVG) rat_count_nonzero(cnt, v[u]);
             for (int j = 1; j <= extra[u]; ++j) {             // MaskedSumPooling bag (padding row is all-zero)
                 int id = idp[u][j];
                 id = id < 0 ? 0 : (id >= vocab[u] ? vocab[u] - 1 : id);
                 const float4 w = *reinterpret_cast<const float4*>(tab[u] + (int64_t)id * d);
                 v[u].x += w.x; v[u].y += w.y; v[u].z += w.z; v[u].w += w.w;
+                if (AVG) rat_count_nonzero(cnt, w);
             }
+            if (AVG && avg[u]) rat_divide_count(v[u], cnt);
         }
 #pragma unroll
         for (int u = 0; u < GATHER_ITEMS; ++u) {
@@ -95,11 +121,11 @@ gather_fwd_vec_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict
 // (242 MB grid, behind the optimizer's sweep) 91-98 us with the hint against 103 us without; alone on the 25.6 GB table at B = 1024
 // (118 MB grid: it fits the 256 MB Infinity Cache, where plain stores are absorbed) 46 us without against 50 us with — so the
 // host asks for the hint only when the grid is larger than what the cache can take.
-template <bool NT>
+template <bool NT, bool AVG>
 __global__ void __launch_bounds__(GATHER_THREADS)
 gather_fwd_rows64_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict__ label_ids,
                          const RatField* __restrict__ fields, const float* __restrict__ label_table,
-                         float* __restrict__ grid, unsigned nrows, unsigned S, int L) {
+                         float* __restrict__ grid, unsigned nrows, unsigned S, int L, const int32_t* __restrict__ modes) {
     constexpr int d = 64;
     const unsigned piece = threadIdx.x & 15;                                    // 16 lanes per 256-byte row
     const unsigned slot = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, nslots = (gridDim.x * blockDim.x) >> 4;
@@ -107,7 +133,7 @@ gather_fwd_rows64_kernel(const int32_t* __restrict__ idx, const int32_t* __restr
         const float* tab[GATHER_ITEMS];
         const int32_t* idp[GATHER_ITEMS];
         int vocab[GATHER_ITEMS], extra[GATHER_ITEMS], id[GATHER_ITEMS];
-        bool ok[GATHER_ITEMS];
+        bool ok[GATHER_ITEMS], avg[GATHER_ITEMS];
 #pragma unroll
         for (int u = 0; u < GATHER_ITEMS; ++u) {
             const unsigned row = r0 + u * nslots;
@@ -120,6 +146,7 @@ gather_fwd_rows64_kernel(const int32_t* __restrict__ idx, const int32_t* __restr
             vocab[u] = lab ? 3 : f.vocab;
             extra[u] = lab ? 0 : f.ncols - 1;
             idp[u] = lab ? label_ids + bt : idx + (int64_t)bt * L + f.col;
+            avg[u] = AVG && !lab && modes[s - 1] != 0;
         }
 #pragma unroll
         for (int u = 0; u < GATHER_ITEMS; ++u) id[u] = *idp[u];
@@ -131,12 +158,16 @@ gather_fwd_rows64_kernel(const int32_t* __restrict__ idx, const int32_t* __restr
         }
 #pragma unroll
         for (int u = 0; u < GATHER_ITEMS; ++u) {
+            Count4 cnt{0, 0, 0, 0};
+            if (AVG) rat_count_nonzero(cnt, v[u]);
             for (int j = 1; j <= extra[u]; ++j) {                                // MaskedSumPooling bag (padding row is all-zero)
                 int i = idp[u][j];
                 i = i < 0 ? 0 : (i >= vocab[u] ? vocab[u] - 1 : i);
                 const float4 w = *(reinterpret_cast<const float4*>(tab[u] + (int64_t)i * d) + piece);
                 v[u].x += w.x; v[u].y += w.y; v[u].z += w.z; v[u].w += w.w;
+                if (AVG) rat_count_nonzero(cnt, w);
             }
+            if (AVG && avg[u]) rat_divide_count(v[u], cnt);
             if (ok[u]) {
                 float* dst = grid + ((size_t)(r0 + u * nslots) * 16 + piece) * 4;
                 if (NT) rat_st4_stream(dst, v[u]);
@@ -147,10 +178,11 @@ gather_fwd_rows64_kernel(const int32_t* __restrict__ idx, const int32_t* __restr
 }
 
 // generic path: any d, one item = one float
+template <bool AVG>
 __global__ void __launch_bounds__(GATHER_THREADS)
 gather_fwd_scalar_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict__ label_ids,
                          const RatField* __restrict__ fields, const float* __restrict__ label_table,
-                         float* __restrict__ grid, int64_t nrows, int S, int L, int d) {
+                         float* __restrict__ grid, int64_t nrows, int S, int L, int d, const int32_t* __restrict__ modes) {
     const int64_t nitems = nrows * d;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nitems; e += (int64_t)gridDim.x * blockDim.x) {
         const int64_t row = e / d;
@@ -166,11 +198,15 @@ gather_fwd_scalar_kernel(const int32_t* __restrict__ idx, const int32_t* __restr
             const RatField f = fields[s - 1];
             const int32_t* ids = idx + bt * L + f.col;
             v = 0.f;
+            int cnt = 0;
             for (int j = 0; j < f.ncols; ++j) {
                 int id = ids[j];
                 id = id < 0 ? 0 : (id >= f.vocab ? f.vocab - 1 : id);
-                v += f.table[(int64_t)id * d + c];
+                const float w = f.table[(int64_t)id * d + c];
+                v += w;
+                if (AVG) cnt += w != 0.f ? 1 : 0;
             }
+            if (AVG && modes[s - 1] != 0) v = v / ((float)cnt + 1e-16f);
         }
         grid[e] = v;
     }
@@ -248,6 +284,40 @@ gather_bwd_fields64_kernel(const float* __restrict__ dgrid, const float* __restr
         int bt0, fi0;
         const float g0 = fetch(r, bt0, fi0);
         scatter(bt0, fi0, g0);
+    }
+}
+
+// Backward of the averaged fields, ahead of the table-gradient stage: the rows of dgrid that belong to an averaged field (every token)
+// and the target's rows of dflat (the DNN input X_emb) are divided by the forward's denominators, in place — torch treats the count
+// as a constant, so every bag id except padding_idx then receives dy / (count + 1e-16f), and the target row's two terms are divided
+// each before the table stage adds them (RAT_m2.py:120,122).  The counts are recomputed from the tables, which no launch changes
+// between a step's forward and its backward.  One wave per (sample row, averaged field): the row decomposition is wave-uniform.
+__global__ void __launch_bounds__(GATHER_THREADS)
+pool_scale_bwd_kernel(float* __restrict__ dgrid, float* __restrict__ dflat, const int32_t* __restrict__ idx,
+                      const RatField* __restrict__ fields, const int32_t* __restrict__ avg_fields, int64_t nrows, int navg, int T,
+                      int S, int L, int d) {
+    const int lane = threadIdx.x & 63;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int F = S - 1;
+    for (int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; r < nrows; r += nwaves) {
+        const int64_t bt = r / navg;
+        const int fi = avg_fields[(int)(r - bt * navg)];
+        const RatField f = fields[fi];
+        const int32_t* ids = idx + bt * L + f.col;
+        const int64_t b = bt / T;
+        float* g0 = dgrid + (bt * S + 1 + fi) * d;
+        float* g1 = (dflat != nullptr && bt - b * T == 0) ? dflat + (b * F + fi) * d : nullptr;
+        for (int c = lane; c < d; c += 64) {
+            int cnt = 0;
+            for (int j = 0; j < f.ncols; ++j) {
+                int id = ids[j];
+                id = id < 0 ? 0 : (id >= f.vocab ? f.vocab - 1 : id);
+                cnt += f.table[(int64_t)id * d + c] != 0.f ? 1 : 0;
+            }
+            const float den = (float)cnt + 1e-16f;
+            g0[c] = g0[c] / den;
+            if (g1 != nullptr) g1[c] = g1[c] / den;
+        }
     }
 }
 
@@ -376,29 +446,54 @@ int pick_blocks(int64_t nitems, int per_thread) {
 
 }  // namespace
 
-extern "C" int rat_gather_fwd(const int32_t* idx, const int32_t* label_ids, const RatField* fields_dev, int nfields,
-                              const float* label_table, float* grid, int B, int T, int L, int d, void* stream) {
-    RAT_REQUIRE(B > 0 && T > 0 && L > 0 && d > 0 && nfields >= 0, "bad dims");
-    RAT_REQUIRE(idx && label_ids && label_table && grid && (fields_dev || nfields == 0), "null pointer");
+template <bool AVG>
+static void gather_fwd_launch(const int32_t* idx, const int32_t* label_ids, const RatField* fields_dev, const int32_t* modes_dev,
+                              int nfields, const float* label_table, float* grid, int B, int T, int L, int d, void* stream) {
     const int S = nfields + 1;
     const int64_t nrows = (int64_t)B * T * S;
     const bool vec = (d % 4 == 0) && ((reinterpret_cast<uintptr_t>(grid) | reinterpret_cast<uintptr_t>(label_table)) % 16 == 0);
     if (vec) {
         if (d == 64 && nrows < (int64_t)0x7fffffff) {
             if (nrows * d * 4 > ((int64_t)160 << 20))
-                RAT_LAUNCH(gather_fwd_rows64_kernel<true>, pick_blocks(nrows * (d / 4), GATHER_ITEMS), GATHER_THREADS, 0, stream, idx,
-                           label_ids, fields_dev, label_table, grid, (unsigned)nrows, (unsigned)S, L);
+                RAT_LAUNCH((gather_fwd_rows64_kernel<true, AVG>), pick_blocks(nrows * (d / 4), GATHER_ITEMS), GATHER_THREADS, 0, stream,
+                           idx, label_ids, fields_dev, label_table, grid, (unsigned)nrows, (unsigned)S, L, modes_dev);
             else
-                RAT_LAUNCH(gather_fwd_rows64_kernel<false>, pick_blocks(nrows * (d / 4), GATHER_ITEMS), GATHER_THREADS, 0, stream, idx,
-                           label_ids, fields_dev, label_table, grid, (unsigned)nrows, (unsigned)S, L);
+                RAT_LAUNCH((gather_fwd_rows64_kernel<false, AVG>), pick_blocks(nrows * (d / 4), GATHER_ITEMS), GATHER_THREADS, 0, stream,
+                           idx, label_ids, fields_dev, label_table, grid, (unsigned)nrows, (unsigned)S, L, modes_dev);
         } else
-            RAT_LAUNCH(gather_fwd_vec_kernel, pick_blocks(nrows * (d / 4), GATHER_ITEMS), GATHER_THREADS, 0, stream, idx,
-                       label_ids, fields_dev, label_table, grid, nrows, S, L, d);
+            RAT_LAUNCH(gather_fwd_vec_kernel<AVG>, pick_blocks(nrows * (d / 4), GATHER_ITEMS), GATHER_THREADS, 0, stream, idx,
+                       label_ids, fields_dev, label_table, grid, nrows, S, L, d, modes_dev);
     } else {
-        RAT_LAUNCH(gather_fwd_scalar_kernel, pick_blocks(nrows * d, 4), GATHER_THREADS, 0, stream, idx, label_ids,
-                   fields_dev, label_table, grid, nrows, S, L, d);
+        RAT_LAUNCH(gather_fwd_scalar_kernel<AVG>, pick_blocks(nrows * d, 4), GATHER_THREADS, 0, stream, idx, label_ids,
+                   fields_dev, label_table, grid, nrows, S, L, d, modes_dev);
     }
+}
+
+extern "C" int rat_gather_fwd(const int32_t* idx, const int32_t* label_ids, const RatField* fields_dev, int nfields,
+                              const float* label_table, float* grid, int B, int T, int L, int d, void* stream) {
+    return rat_gather_fwd_pool(idx, label_ids, fields_dev, nullptr, nfields, label_table, grid, B, T, L, d, stream);
+}
+
+extern "C" int rat_gather_fwd_pool(const int32_t* idx, const int32_t* label_ids, const RatField* fields_dev, const int32_t* modes_dev,
+                                   int nfields, const float* label_table, float* grid, int B, int T, int L, int d, void* stream) {
+    RAT_REQUIRE(B > 0 && T > 0 && L > 0 && d > 0 && nfields >= 0, "bad dims");
+    RAT_REQUIRE(idx && label_ids && label_table && grid && (fields_dev || nfields == 0), "null pointer");
+    if (modes_dev != nullptr && nfields > 0)
+        gather_fwd_launch<true>(idx, label_ids, fields_dev, modes_dev, nfields, label_table, grid, B, T, L, d, stream);
+    else
+        gather_fwd_launch<false>(idx, label_ids, fields_dev, nullptr, nfields, label_table, grid, B, T, L, d, stream);
     return rat_check_launch("rat_gather_fwd");
+}
+
+extern "C" int rat_pool_scale_bwd(float* dgrid, float* dflat, const int32_t* idx, const RatField* fields_dev,
+                                  const int32_t* avg_fields_dev, int navg, int nfields, int B, int T, int L, int d, void* stream) {
+    RAT_REQUIRE(B > 0 && T > 0 && L > 0 && d > 0 && nfields > 0 && navg >= 0 && navg <= nfields, "bad dims");
+    RAT_REQUIRE(dgrid && idx && fields_dev && (avg_fields_dev || navg == 0), "null pointer");
+    if (navg == 0) return 0;
+    const int64_t nrows = (int64_t)B * T * navg;
+    RAT_LAUNCH(pool_scale_bwd_kernel, pick_blocks(nrows * 64, 1), GATHER_THREADS, 0, stream, dgrid, dflat, idx, fields_dev,
+               avg_fields_dev, nrows, navg, T, nfields + 1, L, d);
+    return rat_check_launch("rat_pool_scale_bwd");
 }
 
 extern "C" int rat_gather_bwd(const float* dgrid, const float* dflat, const int32_t* idx, const int32_t* label_ids,

@@ -579,11 +579,15 @@ __device__ __forceinline__ float logit_dot(const float* __restrict__ x, const fl
 
 // 16 lanes per sample: the fc dot over the cls row, the DNN's ONE-output Linear (dnn_in != nullptr: deep.py:135-137, formerly an
 // N = 1 GEMM launch of its own) and the LR lookups are dealt over the lanes and met by a 16-lane sum.
+// AVG (field sets with MaskedAveragePooling fields, modes[f] = 1): each field's LR bag sum is divided by (#{w != 0} + 1e-16f) where
+// averaged, and the denominators (1 for a summed field) go to lr_den [B][nfields] (nullable) for the backward.
+template <bool AVG>
 __global__ void __launch_bounds__(HD_THREADS)
 logit_fwd_kernel(const float* __restrict__ cls, int64_t cls_stride, const float* fc_w, const float* fc_b,
                  const float* dnn_out, const float* __restrict__ dnn_in, int64_t dnn_ld, const float* dnn_w, const float* dnn_b,
                  int dnn_k, const RatField* lr_fields, int nfields, const int32_t* idx, int64_t idx_stride,
-                 const float* y_true, float* y_pred, float* loss_sum, int B, int d, int head, int vec_cls, int vec_dnn) {
+                 const float* y_true, float* y_pred, float* loss_sum, int B, int d, int head, int vec_cls, int vec_dnn,
+                 const int32_t* modes, float* lr_den) {
     RAT_DYN_SMEM(smem);
     float* scratch = reinterpret_cast<float*>(smem);
     const int sub = threadIdx.x % LF_LANES, b = blockIdx.x * LF_SAMPLES + threadIdx.x / LF_LANES;
@@ -596,10 +600,26 @@ logit_fwd_kernel(const float* __restrict__ cls, int64_t cls_stride, const float*
             for (int f = sub; f < nfields; f += LF_LANES) {
                 const RatField fd = lr_fields[f];
                 const int32_t* ids = idx + (int64_t)b * idx_stride + fd.col;
-                for (int j = 0; j < fd.ncols; ++j) {
-                    int id = ids[j];
-                    id = id < 0 ? 0 : (id >= fd.vocab ? fd.vocab - 1 : id);
-                    lr += fd.table[id];
+                if (AVG) {
+                    float sum = 0.f;
+                    int cnt = 0;
+                    for (int j = 0; j < fd.ncols; ++j) {
+                        int id = ids[j];
+                        id = id < 0 ? 0 : (id >= fd.vocab ? fd.vocab - 1 : id);
+                        const float w = fd.table[id];
+                        sum += w;
+                        cnt += w != 0.f ? 1 : 0;
+                    }
+                    const bool avg = modes[f] != 0;
+                    const float den = avg ? (float)cnt + 1e-16f : 1.0f;
+                    lr += avg ? sum / den : sum;
+                    if (lr_den != nullptr) lr_den[(int64_t)b * nfields + f] = den;
+                } else {
+                    for (int j = 0; j < fd.ncols; ++j) {
+                        int id = ids[j];
+                        id = id < 0 ? 0 : (id >= fd.vocab ? fd.vocab - 1 : id);
+                        lr += fd.table[id];
+                    }
                 }
             }
             part += lr;
@@ -633,11 +653,13 @@ logit_fwd_kernel(const float* __restrict__ cls, int64_t cls_stride, const float*
     }
 }
 
+// AVG: field f of sample b scatters dl / lr_den[b][f] (rat_logit_fwd_pool's denominators; 1 for a summed field)
+template <bool AVG>
 __global__ void __launch_bounds__(HD_THREADS)
 logit_bwd_kernel(const float* __restrict__ y_pred, const float* __restrict__ y_true, const float* __restrict__ cls,
                  int64_t cls_stride, const float* fc_w, float* dlogit, float* dcls, int64_t dcls_stride, float* dfc_w,
                  float* dfc_b, float* ddnn_b, const RatField* lr_grad_fields, int nfields, const int32_t* idx, int64_t idx_stride,
-                 float gscale, const float* gscale_dev, int B, int d, int head) {
+                 float gscale, const float* gscale_dev, int B, int d, int head, const float* lr_den) {
     // One block = LB_SAMPLES samples.  Phase 1: thread = (sample, field slot): dlogit and the LR-table atomics of the fields f = slot,
     // slot + 16, ...  Phase 2: thread = (column k, sample group): dcls rows and the dfc_w partial sums, column-parallel, no LDS atomics.
     // ddnn_b (nullable): the bias gradient of the DNN's one-output Linear — the same sum over samples as dfc_b.
@@ -658,10 +680,11 @@ logit_bwd_kernel(const float* __restrict__ y_pred, const float* __restrict__ y_t
                 for (int f = slot; f < nfields; f += HD_THREADS / LB_SAMPLES) {
                     const RatField fd = lr_grad_fields[f];
                     const int32_t* ids = idx + (int64_t)b * idx_stride + fd.col;
+                    const float g = AVG ? dl / lr_den[(int64_t)b * nfields + f] : dl;
                     for (int j = 0; j < fd.ncols; ++j) {
                         int id = ids[j];
                         id = id < 0 ? 0 : (id >= fd.vocab ? fd.vocab - 1 : id);
-                        if (id != fd.padding_idx) atomicAdd(fd.table + id, dl);
+                        if (id != fd.padding_idx) atomicAdd(fd.table + id, g);
                     }
                 }
         }
@@ -744,16 +767,23 @@ extern "C" int rat_colsum(const float* a, int lda, float* out, float* workspace,
 static int logit_fwd_launch(const float* cls, int64_t cls_stride, const float* fc_w, const float* fc_b, const float* dnn_out,
                             const float* dnn_in, int64_t dnn_ld, const float* dnn_w, const float* dnn_b, int dnn_k,
                             const RatField* lr_fields_dev, int nfields, const int32_t* idx, int64_t idx_stride, const float* y_true,
-                            float* y_pred, float* loss_sum, int B, int d, int head, void* stream) {
+                            float* y_pred, float* loss_sum, int B, int d, int head, void* stream, const int32_t* modes_dev = nullptr,
+                            float* lr_den = nullptr) {
     RAT_REQUIRE(B > 0 && d > 0 && cls && fc_w && fc_b && y_pred && (head == 0 || head == 1), "bad args");
     RAT_REQUIRE(lr_fields_dev == nullptr || idx != nullptr, "LR term needs idx");
+    RAT_REQUIRE(lr_den == nullptr || (modes_dev != nullptr && lr_fields_dev != nullptr), "lr_den needs the LR fields and their modes");
     RAT_REQUIRE(dnn_in == nullptr || (dnn_w && dnn_b && dnn_k > 0), "the DNN's output layer needs its weight, bias and width");
     const auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     const int vec_cls = d % 4 == 0 && cls_stride % 4 == 0 && al(cls) && al(fc_w);
     const int vec_dnn = dnn_in != nullptr && dnn_k % 4 == 0 && dnn_ld % 4 == 0 && al(dnn_in) && al(dnn_w);
-    RAT_LAUNCH(logit_fwd_kernel, (B + LF_SAMPLES - 1) / LF_SAMPLES, HD_THREADS, 16 * sizeof(float), stream, cls, cls_stride,
-               fc_w, fc_b, dnn_out, dnn_in, dnn_ld, dnn_w, dnn_b, dnn_k, lr_fields_dev, nfields, idx, idx_stride, y_true, y_pred,
-               loss_sum, B, d, head, vec_cls, vec_dnn);
+    if (modes_dev != nullptr && lr_fields_dev != nullptr)
+        RAT_LAUNCH(logit_fwd_kernel<true>, (B + LF_SAMPLES - 1) / LF_SAMPLES, HD_THREADS, 16 * sizeof(float), stream, cls, cls_stride,
+                   fc_w, fc_b, dnn_out, dnn_in, dnn_ld, dnn_w, dnn_b, dnn_k, lr_fields_dev, nfields, idx, idx_stride, y_true, y_pred,
+                   loss_sum, B, d, head, vec_cls, vec_dnn, modes_dev, lr_den);
+    else
+        RAT_LAUNCH(logit_fwd_kernel<false>, (B + LF_SAMPLES - 1) / LF_SAMPLES, HD_THREADS, 16 * sizeof(float), stream, cls, cls_stride,
+                   fc_w, fc_b, dnn_out, dnn_in, dnn_ld, dnn_w, dnn_b, dnn_k, lr_fields_dev, nfields, idx, idx_stride, y_true, y_pred,
+                   loss_sum, B, d, head, vec_cls, vec_dnn, nullptr, nullptr);
     return rat_check_launch("rat_logit_fwd");
 }
 
@@ -776,13 +806,18 @@ extern "C" int rat_logit_fwd_dnn(const float* cls, int64_t cls_stride, const flo
 static int logit_bwd_launch(const float* y_pred, const float* y_true, const float* cls, int64_t cls_stride, const float* fc_w,
                             float* dlogit, float* dcls, int64_t dcls_stride, float* dfc_w, float* dfc_b, float* ddnn_b,
                             const RatField* lr_grad_fields_dev, int nfields, const int32_t* idx, int64_t idx_stride, float gscale,
-                            const float* gscale_dev, int B, int d, int head, void* stream) {
+                            const float* gscale_dev, int B, int d, int head, void* stream, const float* lr_den = nullptr) {
     RAT_REQUIRE(B > 0 && d > 0 && y_pred && y_true && cls && fc_w && dlogit && dcls && dfc_w && dfc_b && (head == 0 || head == 1), "bad args");
     RAT_REQUIRE(lr_grad_fields_dev == nullptr || idx != nullptr, "LR term needs idx");
     RAT_REQUIRE(d <= HD_THREADS, "embedding_dim above the block size");
-    RAT_LAUNCH(logit_bwd_kernel, (B + LB_SAMPLES - 1) / LB_SAMPLES, HD_THREADS, (size_t)(LB_SAMPLES + HD_THREADS) * sizeof(float), stream,
-               y_pred, y_true, cls, cls_stride, fc_w, dlogit, dcls, dcls_stride, dfc_w, dfc_b, ddnn_b, lr_grad_fields_dev, nfields,
-               idx, idx_stride, gscale, gscale_dev, B, d, head);
+    if (lr_den != nullptr && lr_grad_fields_dev != nullptr)
+        RAT_LAUNCH(logit_bwd_kernel<true>, (B + LB_SAMPLES - 1) / LB_SAMPLES, HD_THREADS, (size_t)(LB_SAMPLES + HD_THREADS) * sizeof(float),
+                   stream, y_pred, y_true, cls, cls_stride, fc_w, dlogit, dcls, dcls_stride, dfc_w, dfc_b, ddnn_b, lr_grad_fields_dev,
+                   nfields, idx, idx_stride, gscale, gscale_dev, B, d, head, lr_den);
+    else
+        RAT_LAUNCH(logit_bwd_kernel<false>, (B + LB_SAMPLES - 1) / LB_SAMPLES, HD_THREADS, (size_t)(LB_SAMPLES + HD_THREADS) * sizeof(float),
+                   stream, y_pred, y_true, cls, cls_stride, fc_w, dlogit, dcls, dcls_stride, dfc_w, dfc_b, ddnn_b, lr_grad_fields_dev,
+                   nfields, idx, idx_stride, gscale, gscale_dev, B, d, head, nullptr);
     return rat_check_launch("rat_logit_bwd");
 }
 
@@ -801,6 +836,32 @@ extern "C" int rat_logit_bwd_dnn(const float* y_pred, const float* y_true, const
     RAT_REQUIRE(ddnn_b != nullptr, "null ddnn_b");
     return logit_bwd_launch(y_pred, y_true, cls, cls_stride, fc_w, dlogit, dcls, dcls_stride, dfc_w, dfc_b, ddnn_b, lr_grad_fields_dev,
                             nfields, idx, idx_stride, gscale, gscale_dev, B, d, head, stream);
+}
+
+extern "C" int rat_logit_fwd_pool(const float* cls, int64_t cls_stride, const float* fc_w, const float* fc_b, const float* dnn_out,
+                                  const RatField* lr_fields_dev, const int32_t* modes_dev, int nfields, const int32_t* idx,
+                                  int64_t idx_stride, const float* y_true, float* y_pred, float* loss_sum, float* lr_den, int B, int d,
+                                  int head, void* stream) {
+    return logit_fwd_launch(cls, cls_stride, fc_w, fc_b, dnn_out, nullptr, 0, nullptr, nullptr, 0, lr_fields_dev, nfields, idx,
+                            idx_stride, y_true, y_pred, loss_sum, B, d, head, stream, modes_dev, lr_den);
+}
+
+extern "C" int rat_logit_fwd_dnn_pool(const float* cls, int64_t cls_stride, const float* fc_w, const float* fc_b, const float* dnn_in,
+                                      int64_t dnn_ld, const float* dnn_w, const float* dnn_b, int dnn_k, const RatField* lr_fields_dev,
+                                      const int32_t* modes_dev, int nfields, const int32_t* idx, int64_t idx_stride,
+                                      const float* y_true, float* y_pred, float* loss_sum, float* lr_den, int B, int d, int head,
+                                      void* stream) {
+    RAT_REQUIRE(dnn_in != nullptr, "null dnn_in");
+    return logit_fwd_launch(cls, cls_stride, fc_w, fc_b, nullptr, dnn_in, dnn_ld, dnn_w, dnn_b, dnn_k, lr_fields_dev, nfields, idx,
+                            idx_stride, y_true, y_pred, loss_sum, B, d, head, stream, modes_dev, lr_den);
+}
+
+extern "C" int rat_logit_bwd_pool(const float* y_pred, const float* y_true, const float* cls, int64_t cls_stride, const float* fc_w,
+                                  float* dlogit, float* dcls, int64_t dcls_stride, float* dfc_w, float* dfc_b, float* ddnn_b,
+                                  const RatField* lr_grad_fields_dev, const float* lr_den, int nfields, const int32_t* idx,
+                                  int64_t idx_stride, float gscale, const float* gscale_dev, int B, int d, int head, void* stream) {
+    return logit_bwd_launch(y_pred, y_true, cls, cls_stride, fc_w, dlogit, dcls, dcls_stride, dfc_w, dfc_b, ddnn_b, lr_grad_fields_dev,
+                            nfields, idx, idx_stride, gscale, gscale_dev, B, d, head, stream, lr_den);
 }
 
 extern "C" int rat_bn_relu_bwd(const float* z, const float* a, const float* da, float* dz, const float* gamma,

@@ -178,6 +178,7 @@ unsigned bits_for(uint64_t maxval) {
 
 // ---- reduce -----------------------------------------------------------------------------------------------------
 // SRC 0: token grid (+ DNN-branch rows on the target sample)   SRC 1: row list   SRC 2: one scalar per sample (width 1)
+// SRC 3: SRC 2 divided per (sample, field) by den [B][F] (averaged LR fields: rat_logit_fwd_pool's denominators)
 struct ReduceArgs {
     const uint32_t* keys;
     const uint32_t* vals;
@@ -187,6 +188,7 @@ struct ReduceArgs {
     const float* src;        // dgrid / gathered rows / dlogit
     const float* dflat;      // SRC 0 only (nullable)
     const int32_t* col2field;
+    const float* den;        // SRC 3 only: [B][F]
     int T, L, S, F, d, target_only;
     int32_t* out_rows;       // nullable
     float* out_grads;        // nullable: [segment][d]
@@ -201,7 +203,7 @@ __device__ __forceinline__ void entry_sources(const ReduceArgs& a, uint32_t pos,
     } else {
         const int64_t r = pos / a.L;
         const int c = (int)(pos - r * a.L);
-        if (SRC == 2) {
+        if (SRC == 2 || SRC == 3) {
             p0 = a.src + r;                                        // dlogit[b]: the plan ran over the target rows only
         } else {
             const int64_t bt = a.target_only ? r * a.T : r;
@@ -255,7 +257,13 @@ __global__ void __launch_bounds__(SP_THREADS) reduce_scalar_kernel(ReduceArgs a)
             const float* p0;
             const float* p1;
             entry_sources<SRC>(a, a.vals[e], p0, p1);
-            float v = p0[SRC == 2 ? 0 : c];
+            float v = p0[SRC >= 2 ? 0 : c];
+            if (SRC == 3) {
+                const uint32_t pos = a.vals[e];
+                const int64_t r = pos / a.L;
+                const int fi = a.col2field[pos - r * a.L];
+                if (fi >= 0) v = v / a.den[r * a.F + fi];
+            }
             if (p1 != nullptr) v += p1[c];
             acc += v;
         }
@@ -269,7 +277,11 @@ __global__ void __launch_bounds__(SP_THREADS) reduce_scalar_kernel(ReduceArgs a)
 template <int SRC>
 int launch_reduce(const ReduceArgs& a, bool aligned, void* stream) {
     const int64_t segs = a.max_segments;
-    if (a.d % 4 == 0 && aligned && SRC != 2) {
+    if constexpr (SRC == 3) {                                    // width 1 only: no vector instantiation
+        int64_t blocks = (segs * a.d + SP_THREADS - 1) / SP_THREADS;
+        blocks = blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks);
+        RAT_LAUNCH((reduce_scalar_kernel<SRC>), (unsigned)blocks, SP_THREADS, 0, stream, a);
+    } else if (a.d % 4 == 0 && aligned && SRC != 2) {
         const int c4 = a.d / 4;
         const int G = c4 <= 1 ? 1 : c4 <= 2 ? 2 : c4 <= 4 ? 4 : c4 <= 8 ? 8 : c4 <= 16 ? 16 : c4 <= 32 ? 32 : 64;
         RAT_REQUIRE(c4 <= 64, "row width above 256 floats");
@@ -580,6 +592,22 @@ extern "C" int rat_sparse_reduce_scalar(const void* workspace, const int32_t* co
     a.src = per_sample; a.d = 1; a.L = L; a.T = 1; a.target_only = 1;
     a.out_rows = out_rows; a.out_grads = out_vals; a.dense_base = dense_base;
     return launch_reduce<2>(a, false, stream);
+}
+
+extern "C" int rat_sparse_reduce_scalar_pool(const void* workspace, const int32_t* count_dev, const float* per_sample, const float* lr_den,
+                                             const int32_t* col2field_dev, int nfields, int B, int L, int32_t* out_rows, float* out_vals,
+                                             float* dense_base, void* stream) {
+    if (lr_den == nullptr) return rat_sparse_reduce_scalar(workspace, count_dev, per_sample, B, L, out_rows, out_vals, dense_base, stream);
+    RAT_REQUIRE(workspace && count_dev && per_sample && col2field_dev && (out_vals || dense_base) && B > 0 && L > 0 && nfields > 0,
+                "bad args");
+    const int64_t n = (int64_t)B * L;
+    PlanView v = carve(const_cast<void*>(workspace), n);
+    ReduceArgs a{};
+    a.keys = v.keys_b; a.vals = v.vals_b; a.seg_start = v.seg_start; a.count = count_dev; a.max_segments = n;
+    a.src = per_sample; a.d = 1; a.L = L; a.T = 1; a.target_only = 1;
+    a.col2field = col2field_dev; a.den = lr_den; a.F = nfields;
+    a.out_rows = out_rows; a.out_grads = out_vals; a.dense_base = dense_base;
+    return launch_reduce<3>(a, false, stream);
 }
 
 extern "C" int rat_sumsq_rows(const float* grads, const int32_t* count_dev, int64_t max_rows, int d, float* norm_sq_out, void* stream) {

@@ -142,6 +142,15 @@ _SIGNATURES = {
     "rat_owner_unpack": (c_int, [_P, c_int, c_int, c_int, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
     "rat_owner_scatter": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int64, c_int64, c_int, c_int, _P]),
     "rat_adam_rows_dev": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int, _P, c_float, _P, c_float, c_float, c_float, _P]),
+    # MaskedAveragePooling fields (per-field mode arrays; a NULL array is the entry point above without "_pool")
+    "rat_gather_fwd_pool": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "rat_pool_scale_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "rat_logit_fwd_pool": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, c_int, _P, c_int64, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "rat_logit_fwd_dnn_pool": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, _P, c_int, _P, _P, c_int, _P, c_int64, _P, _P, _P, _P, c_int,
+                                       c_int, c_int, _P]),
+    "rat_logit_bwd_pool": (c_int, [_P, _P, _P, c_int64, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int, _P, c_int64, c_float, _P, c_int,
+                                   c_int, c_int, _P]),
+    "rat_sparse_reduce_scalar_pool": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -49,12 +49,15 @@ class FeatureMap:
 
 
 class FieldInfo:
-    """Per-field record handed to the kernels (include/rat_hip.h RatField minus the table pointer)."""
-    __slots__ = ("name", "kind", "col", "ncols", "vocab", "padding_idx")
+    """Per-field record handed to the kernels (include/rat_hip.h RatField minus the table pointer).
+    pooling: "sum" (categorical fields, MaskedSumPooling) or "average" (MaskedAveragePooling, sequence.py:21-29) — the per-field
+    mode the *_pool entry points take."""
+    __slots__ = ("name", "kind", "col", "ncols", "vocab", "padding_idx", "pooling")
 
     def __init__(self, name, spec):
         self.name = name
         self.kind = spec["type"]
+        self.pooling = "sum"
         index = spec["index"]
         if self.kind == "categorical":
             self.col, self.ncols = int(index), 1
@@ -64,7 +67,9 @@ class FieldInfo:
             if cols != list(range(cols[0], cols[0] + len(cols))):
                 raise NotImplementedError("sequence field %s: non-contiguous columns" % name)
             enc = spec.get("encoder", None)
-            if enc != "MaskedSumPooling":
+            if enc == "MaskedAveragePooling":
+                self.pooling = "average"
+            elif enc != "MaskedSumPooling":
                 raise NotImplementedError("sequence encoder %r is outside the RAT_m2 hot path "
                                           "(only MaskedSumPooling is used by the shipped configs)" % (enc,))
             self.col, self.ncols = int(cols[0]), len(cols)

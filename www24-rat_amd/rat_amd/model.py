@@ -662,6 +662,11 @@ class RAT_m2(DataParallelExchange, BaseModel):
             self._lr_ftab = ops.field_table(self._fields, self._lr_tables, dev)
         else:
             self._lr_tables, self._lr_ftab = None, None
+        # MaskedAveragePooling fields: per-field modes for the *_pool entry points and the averaged fields' indices for the backward's
+        # scale pass; both None for a sum-only field set, which then runs the sum-only entry points unchanged
+        self._pool_modes = ops.pool_modes(self._fields, dev)
+        self._avg_fields = None if self._pool_modes is None else torch.tensor(
+            [i for i, f in enumerate(self._fields) if f.pooling == "average"], dtype=torch.int32, device=dev)
         self._col2field = None                                  # built on first use (needs the batch's column count)
         self._build_encoder_descriptors()
         # DNN head layout: [(linear_idx, bn_idx or None, dropout_p)], out linear idx
@@ -1039,7 +1044,8 @@ class RAT_m2(DataParallelExchange, BaseModel):
             if self._id_errors is None:
                 self._id_errors = torch.zeros(2, dtype=torch.int32, device=idx.device)
             ops.check_ids(idx, labels, self._ftab, F, self._id_errors, B, T, L, lib=lib)
-        x0 = ops.gather_fwd(idx, labels, self._ftab, F, self._p("label_embedding_layer.weight"), B, T, L, d, lib=lib)
+        x0 = ops.gather_fwd(idx, labels, self._ftab, F, self._p("label_embedding_layer.weight"), B, T, L, d, modes=self._pool_modes,
+                            lib=lib)
         saved = {"batch": batch, "dims": (B, T, L, S), "blocks": [], "dnn": []}
         # dropout: the masks are counter-based functions of per-layer seed WORDS that live on the device and are refreshed once per
         # training forward (rat_dropout_seeds) — no host draw per step, so a captured step replays with new masks; backward re-derives
@@ -1097,11 +1103,15 @@ class RAT_m2(DataParallelExchange, BaseModel):
         loss = self.__dict__.pop("_step_loss", None)                      # the fused iteration's zeroed scalar (one fill per step)
         if loss is None:
             loss = torch.zeros(1, dtype=torch.float32, device=x0.device)
+        lr_den = None                                                       # averaged LR fields: the denominators the backward divides by
+        if save and self._pool_modes is not None and self._lr_ftab is not None:
+            lr_den = torch.empty((B, F), dtype=torch.float32, device=x0.device)
         y_pred = ops.logit_fwd(x, cls_stride, self.fc.weight.data, self.fc.bias.data, dnn_out, self._lr_ftab, F, idx, T * L,
-                               y_true, loss, B, d, head=self._head, dnn_last=dnn_last, lib=lib)
+                               y_true, loss, B, d, head=self._head, dnn_last=dnn_last, modes=self._pool_modes, lr_den=lr_den, lib=lib)
         reg = self._regularization_value() if with_reg else None
         if save:
             saved["x_final"], saved["cls_stride"], saved["y_pred"] = x, cls_stride, y_pred
+            saved["lr_den"] = lr_den
         return y_pred, loss[0], reg, saved
 
     _DROP_WORDS = 64
@@ -1220,7 +1230,7 @@ class RAT_m2(DataParallelExchange, BaseModel):
         pre_out = "dnn.dnn.%d." % self._dnn_out if self.dnn is not None else None
         dlogit = ops.logit_bwd(y_pred, y_true, x_final, cs, self.fc.weight.data, dx, dcs, G("fc.weight"),
                                G("fc.bias"), lr_gftab, F, idx, T * L, 1.0, B, d, gscale_dev=g_loss, head=self._head,
-                               ddnn_b=G(pre_out + "bias") if fold else None, lib=lib)
+                               ddnn_b=G(pre_out + "bias") if fold else None, lr_den=saved.get("lr_den"), lib=lib)
         dflat = None
         if self.dnn is not None:
             mods = self.dnn.dnn
@@ -1300,11 +1310,15 @@ class RAT_m2(DataParallelExchange, BaseModel):
         if saved["seeds"] is not None and c["emb_dropout"] > 0:
             dx = ops.dropout(dx, c["emb_dropout"], saved["seeds"][0], out=dx, lib=lib)
         # ---- embedding tables
+        if self._avg_fields is not None:
+            # MaskedAveragePooling backward: the averaged rows of dx / dflat are divided by their denominators in place — both are
+            # read by nothing but the table stage below (whose label-row pass reads the unscaled rows s = 0), on every path
+            ops.pool_scale_bwd(dx, dflat, idx, self._ftab, self._avg_fields, F, B, T, L, d, lib=lib)
         if mode == "atomic":
             ops.gather_bwd(dx, dflat, idx, labels, gftab, F, G("label_embedding_layer.weight"), B, T, L, d, lib=lib)
             self._sparse = None
         else:
-            self._table_gradients_sorted(dx, dflat, dlogit, idx, labels, gflat, (B, T, L, S), mode)
+            self._table_gradients_sorted(dx, dflat, dlogit, idx, labels, gflat, (B, T, L, S), mode, lr_den=saved.get("lr_den"))
             ops.label_grad(dx, labels, G("label_embedding_layer.weight"), B * T, S, d, lib=lib)
             if as_lists:
                 self._table_lists, self._sparse = self._sparse, None
@@ -1316,10 +1330,11 @@ class RAT_m2(DataParallelExchange, BaseModel):
         self._last_gflat = gflat
         return [self._gflat_view(gflat, n) if self._offsets[n] >= self._n_sparse else None for n in self._order]
 
-    def _table_gradients_sorted(self, dx, dflat, dlogit, idx, labels, gflat, dims, mode):
+    def _table_gradients_sorted(self, dx, dflat, dlogit, idx, labels, gflat, dims, mode, lr_den=None):
         """K1s: stable sort of the batch's (sample, id column) pairs by table row + segmented reduction in batch order.
         mode "sorted": sums land in the dense gradient tables (bit-reproducible replacement of the fp32 atomics);
-        mode "sparse": (unique rows, gradient rows, count) lists per table family, consumed by rat_adam_rows."""
+        mode "sparse": (unique rows, gradient rows, count) lists per table family, consumed by rat_adam_rows.
+        lr_den: the forward's LR denominators when some field averages (the LR rows then receive dlogit / denominator)."""
         c, lib = self._cfg, self._lib
         B, T, L, S = dims
         d, F = c["d"], c["nf"]
@@ -1340,12 +1355,14 @@ class RAT_m2(DataParallelExchange, BaseModel):
         if c["use_wide"]:                                       # LR tables: width-1 rows, gradient = dlogit of the TARGET sample
             rows_lr = self._n_tab - self._n_feat
             if mode == "sorted":
-                ops.sparse_reduce_scalar(plan_lr, dlogit, B, L, dense_base=gflat[self._n_feat:], lib=lib)
+                ops.sparse_reduce_scalar(plan_lr, dlogit, B, L, dense_base=gflat[self._n_feat:], lr_den=lr_den, col2field=self._col2field,
+                                         lib=lib)
             else:
                 cap = min(B * L, rows_lr)
                 rows = torch.empty(cap, dtype=torch.int32, device=dev)
                 vals = torch.empty((cap, 1), dtype=torch.float32, device=dev)
-                ops.sparse_reduce_scalar(plan_lr, dlogit, B, L, out_rows=rows, out_vals=vals, lib=lib)
+                ops.sparse_reduce_scalar(plan_lr, dlogit, B, L, out_rows=rows, out_vals=vals, lr_den=lr_den, col2field=self._col2field,
+                                         lib=lib)
                 sparse.append((rows, vals, plan_lr.count.clone(), 1, rows_lr, self._n_feat))
         self._sparse = sparse if mode in ("sparse", "lists") else None
         self._sparse_is_global = False

@@ -171,12 +171,36 @@ def batch_prepare(X, y, out=None, lib=None):
     return idx, labels, y_true
 
 
-def gather_fwd(idx, label_ids, ftab, nfields, label_table, B, T, L, d, lib=None):
+def pool_modes(fields, device):
+    """int32 [F] per-field pooling modes (0 = sum / categorical, 1 = MaskedAveragePooling), or None when no field averages —
+    the sum-only entry points then run unchanged"""
+    modes = [1 if getattr(f, "pooling", "sum") == "average" else 0 for f in fields]
+    if not any(modes):
+        return None
+    return torch.tensor(modes, dtype=torch.int32, device=device)
+
+
+def gather_fwd(idx, label_ids, ftab, nfields, label_table, B, T, L, d, modes=None, lib=None):
+    """modes: pool_modes(...) (None: every field sums)"""
     lib = lib or get_lib()
     _chk(idx, torch.int32, "idx"), _chk(label_ids, torch.int32, "label_ids"), _chk(label_table, name="label_table")
     grid = torch.empty((B, T, nfields + 1, d), dtype=torch.float32, device=idx.device)
+    if modes is not None:
+        _chk(modes, torch.int32, "modes")
+        lib.call("rat_gather_fwd_pool", _p(idx), _p(label_ids), _p(ftab), _p(modes), nfields, _p(label_table), _p(grid), B, T, L, d,
+                 _stream(idx))
+        return grid
     lib.call("rat_gather_fwd", _p(idx), _p(label_ids), _p(ftab), nfields, _p(label_table), _p(grid), B, T, L, d, _stream(idx))
     return grid
+
+
+def pool_scale_bwd(dgrid, dflat, idx, ftab, avg_fields, nfields, B, T, L, d, lib=None):
+    """divides, in place, the averaged fields' rows of dgrid (and their target rows of dflat) by the forward's denominators;
+    avg_fields: int32 [navg] device tensor of averaged field indices"""
+    lib = lib or get_lib()
+    _chk(dgrid, name="dgrid"), _chk(dflat, name="dflat"), _chk(idx, torch.int32, "idx"), _chk(avg_fields, torch.int32, "avg_fields")
+    lib.call("rat_pool_scale_bwd", _p(dgrid), _p(dflat), _p(idx), _p(ftab), _p(avg_fields), avg_fields.numel(), nfields, B, T, L, d,
+             _stream(dgrid))
 
 
 def check_ids(idx, label_ids, ftab, nfields, counts, B, T, L, lib=None):
@@ -252,9 +276,15 @@ def sparse_reduce_rows(plan, src_rows, cap, world, d, out_rows, out_grads, count
              _p(out_rows), _p(out_grads), _stream(src_rows))
 
 
-def sparse_reduce_scalar(plan, per_sample, B, L, out_rows=None, out_vals=None, dense_base=None, lib=None):
+def sparse_reduce_scalar(plan, per_sample, B, L, out_rows=None, out_vals=None, dense_base=None, lr_den=None, col2field=None, lib=None):
+    """lr_den: [B][F] denominators of logit_fwd(..., lr_den=...) (averaged LR fields) with the col2field table they are indexed by"""
     lib = lib or get_lib()
     _chk(per_sample, name="per_sample"), _chk(out_vals, name="out_vals"), _chk(out_rows, torch.int32, "out_rows")
+    if lr_den is not None:
+        _chk(lr_den, name="lr_den"), _chk(col2field, torch.int32, "col2field")
+        lib.call("rat_sparse_reduce_scalar_pool", _p(plan.ws), _p(plan.count), _p(per_sample), _p(lr_den), _p(col2field), lr_den.shape[1],
+                 B, L, _p(out_rows), _p(out_vals), _p(dense_base), _stream(per_sample))
+        return
     lib.call("rat_sparse_reduce_scalar", _p(plan.ws), _p(plan.count), _p(per_sample), B, L, _p(out_rows), _p(out_vals), _p(dense_base),
              _stream(per_sample))
 
@@ -700,11 +730,23 @@ def colsum(a, lda, out, M, N, lib=None):
 
 
 def logit_fwd(cls, cls_stride, fc_w, fc_b, dnn_out, lr_ftab, nfields, idx, idx_stride, y_true, loss_sum, B, d, head=0, dnn_last=None,
-              lib=None):
+              modes=None, lr_den=None, lib=None):
     """head: 0 = sigmoid + binary cross-entropy, 1 = no output activation + mean squared error (task "regression")
-    dnn_last = (a [B][K], lda, K, w [1][K], b [1]): the DNN's one-output Linear is evaluated inside the launch (dnn_out must be None)"""
+    dnn_last = (a [B][K], lda, K, w [1][K], b [1]): the DNN's one-output Linear is evaluated inside the launch (dnn_out must be None)
+    modes: pool_modes(...) of the LR fields (None: every field sums); lr_den (with modes): float [B][nfields] <- the LR denominators"""
     lib = lib or get_lib()
     y_pred = torch.empty((B, 1), dtype=torch.float32, device=fc_w.device)
+    if modes is not None and lr_ftab is not None:
+        _chk(modes, torch.int32, "modes"), _chk(lr_den, name="lr_den")
+        if dnn_last is not None:
+            assert dnn_out is None
+            a, lda, K, w, b = dnn_last
+            lib.call("rat_logit_fwd_dnn_pool", _p(cls), cls_stride, _p(fc_w), _p(fc_b), _p(a), lda, _p(w), _p(b), K, _p(lr_ftab), _p(modes),
+                     nfields, _p(idx), idx_stride, _p(y_true), _p(y_pred), _p(loss_sum), _p(lr_den), B, d, int(head), _stream(fc_w))
+        else:
+            lib.call("rat_logit_fwd_pool", _p(cls), cls_stride, _p(fc_w), _p(fc_b), _p(dnn_out), _p(lr_ftab), _p(modes), nfields, _p(idx),
+                     idx_stride, _p(y_true), _p(y_pred), _p(loss_sum), _p(lr_den), B, d, int(head), _stream(fc_w))
+        return y_pred
     if dnn_last is not None:
         assert dnn_out is None
         a, lda, K, w, b = dnn_last
@@ -717,11 +759,18 @@ def logit_fwd(cls, cls_stride, fc_w, fc_b, dnn_out, lr_ftab, nfields, idx, idx_s
 
 
 def logit_bwd(y_pred, y_true, cls, cls_stride, fc_w, dcls, dcls_stride, dfc_w, dfc_b, lr_gftab, nfields, idx, idx_stride,
-              gscale, B, d, gscale_dev=None, head=0, ddnn_b=None, lib=None):
+              gscale, B, d, gscale_dev=None, head=0, ddnn_b=None, lr_den=None, lib=None):
     """gscale: host factor; gscale_dev: optional DEVICE scalar multiplied in by the kernel (autograd's incoming gradient).
-    ddnn_b: also accumulate sum_b dlogit[b] there (bias gradient of the DNN's one-output Linear)"""
+    ddnn_b: also accumulate sum_b dlogit[b] there (bias gradient of the DNN's one-output Linear)
+    lr_den: the LR denominators logit_fwd wrote (averaged LR fields): field f of sample b scatters dlogit[b] / lr_den[b][f]"""
     lib = lib or get_lib()
     dlogit = torch.empty((B, 1), dtype=torch.float32, device=fc_w.device)
+    if lr_den is not None and lr_gftab is not None:
+        _chk(lr_den, name="lr_den")
+        lib.call("rat_logit_bwd_pool", _p(y_pred), _p(y_true), _p(cls), cls_stride, _p(fc_w), _p(dlogit), _p(dcls), dcls_stride,
+                 _p(dfc_w), _p(dfc_b), _p(ddnn_b), _p(lr_gftab), _p(lr_den), nfields, _p(idx), idx_stride, float(gscale), _p(gscale_dev),
+                 B, d, int(head), _stream(fc_w))
+        return dlogit
     if ddnn_b is not None:
         lib.call("rat_logit_bwd_dnn", _p(y_pred), _p(y_true), _p(cls), cls_stride, _p(fc_w), _p(dlogit), _p(dcls), dcls_stride,
                  _p(dfc_w), _p(dfc_b), _p(ddnn_b), _p(lr_gftab), nfields, _p(idx), idx_stride, float(gscale), _p(gscale_dev), B, d,
