@@ -330,6 +330,31 @@ int rat_bm25_topk_grouped(const int32_t* db_ids_field_major, const int32_t* db_g
                           const double* qry_idf, const int32_t* qry_groups, double* out_values, int64_t* out_indices,
                           int64_t* out_lens, int64_t n_db, int64_t n_qry, int n_fields, int topk, void* stream);
 
+/* ---- K6b: the request path (online scoring; additive in ABI v9) ----------------------------------------------------
+ * map_data_to_IDF_v1 (data_utils.py:843-847) for ONE query batch on the device.  ids [n_qry][row_stride] int32 are full encoded rows,
+ * cols [n_fields] int32 the columns the retrieval compares; the pool's per-column IDF tables are three flat arrays: table_ids (sorted
+ * distinct ids of column 0, then column 1, ...), table_idf (their weights, float64 = log(n_db / count)) and table_offsets
+ * [n_fields + 1] int64.  Outputs are exactly rat_bm25_topk's query inputs: qry_ids [n_qry][n_fields] = the gathered columns,
+ * qry_idf [n_qry][n_fields] = the id's weight, 0 for ids the pool column does not hold — and, bug-compatible with the reference's
+ * np.vectorize (its output dtype comes from the first element): if row 0 OF THIS CALL misses in a column, every weight of that column
+ * is truncated toward zero.  n_fields <= 32. */
+int rat_bm25_query_prepare(const int32_t* ids, const int32_t* cols, const int32_t* table_ids, const double* table_idf,
+                           const int64_t* table_offsets, int32_t* qry_ids, double* qry_idf, int64_t n_qry, int row_stride,
+                           int n_fields, void* stream);
+
+/* rat_bm25_topk's contract (same inputs, same outputs, same tie rule, same limits) for FEW queries: the pool is cut into `splits`
+ * contiguous row ranges of ceil(n_db / splits) rows scanned by different work-groups (ranges past the end are empty), each leaves its
+ * topk best in `workspace` ([n_qry][splits][topk] float64 scores, then as many int64 indices), and a second launch merges them by
+ * (score descending, index ascending).  The scores are the same float64 sums in the same order and that order is total, so the
+ * result equals rat_bm25_topk's BIT FOR BIT for every splits >= 1 (<= 4096).  splits = 0: the library chooses from (n_qry, n_db) —
+ * when the query tiles alone fill the chip it runs rat_bm25_topk itself and touches no workspace.  workspace_bytes >=
+ * rat_bm25_topk_split_workspace(n_qry, topk, splits) (for splits = 0: the most the library may choose for that many queries),
+ * 8-byte aligned.  Two launches on `stream`, no allocation, no synchronisation, no floating-point atomics: capturable. */
+size_t rat_bm25_topk_split_workspace(int64_t n_qry, int topk, int splits);
+int rat_bm25_topk_split(const int32_t* db_ids_field_major, const int32_t* qry_ids, const double* qry_idf, double* out_values,
+                        int64_t* out_indices, int64_t* out_lens, void* workspace, size_t workspace_bytes, int64_t n_db,
+                        int64_t n_qry, int n_fields, int topk, int splits, void* stream);
+
 /* ---- K3: prediction head -----------------------------------------------------------------------------
  * Plain fp32 GEMM on MFMA for MLP_Layer's nn.Linear (deep.py:126-141) forward / dgrad / wgrad:
  * C[M][N] = op(A) op(B) (+ bias[N]) (+ beta*C), row-major with leading dimensions, op = transpose flag. */

@@ -1,0 +1,175 @@
+#!/usr/bin/env python3
+"""Diagnostic: the request path of the retrieval and of online scoring on the MI355X.
+
+    python tools/online_bench.py [--out profiles/online/online_bench.txt] [--quick]
+
+Part 1 — for N in {100 k, 1.4 M} pool rows, F in {3, 13} columns, K = 5 and Q in {1, 4, 16, 64, 256, 4096} queries: rat_bm25_topk
+(the offline kernel: one work-group per tile of four queries scans the whole pool) against rat_bm25_topk_split with splits = 0 (the
+library's choice) and a sweep of explicit range counts.  Same process, the variants alternating, outputs compared for equality
+before anything is timed.  Every variant is captured as a hipGraph of REPS back-to-back calls and the replays are timed with device
+events (warm-up replays first, at least 0.5 s of timed work per point), so a figure is device time per call, free of launch issue.
+Part 2 — latency of OnlineScorer.score() (retrieve -> assemble -> eval forward), eager and replayed, at B in {1, 16, 256} for the
+MovieLens-real geometry (movielens_real_F3_K5_d10_B4096's model, 1.4 M-row synthetic pool): host clock around score() + synchronise.
+There is no CPU fallback: without a GPU the tool exits with an error."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "www24-rat_amd")):
+    sys.path.insert(0, p)
+
+REPS = 20
+MIN_TIMED_MS = 500.0
+SWEEP = (2, 8, 32, 64, 128, 256, 512)
+
+
+def _graph_of(fn, reps):
+    g = torch.cuda.CUDAGraph()
+    stream = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.graph(g, stream=stream, capture_error_mode="thread_local"):
+        for _ in range(reps):
+            out = fn()
+    return g, out
+
+
+def time_alternating(graphs, reps, min_ms):
+    """graphs: {label: CUDAGraph of `reps` calls} -> {label: ms per call}; round-robin replays until every label has min_ms"""
+    for g in graphs.values():
+        for _ in range(3):
+            g.replay()
+    torch.cuda.synchronize()
+    total = {k: 0.0 for k in graphs}
+    count = {k: 0 for k in graphs}
+    while min(total.values()) < min_ms:
+        pending = []
+        for k, g in graphs.items():
+            if total[k] >= min_ms and count[k] >= 3:
+                continue
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            g.replay()
+            e.record()
+            pending.append((k, s, e))
+        torch.cuda.synchronize()
+        for k, s, e in pending:
+            total[k] += s.elapsed_time(e)
+            count[k] += 1
+    return {k: total[k] / (count[k] * reps) for k in graphs}
+
+
+def part1(emit, quick):
+    import ctypes
+    from rat_amd import ops, retrieval
+    from rat_amd._lib import get_lib
+    lib = get_lib()
+    dev = torch.device("cuda:0")
+    K = 5
+    emit("== part 1: device time per call [us], K = %d; split(s) = rat_bm25_topk_split with s ranges, split(0) = the library's choice" % K)
+    worst_auto = 0.0
+    for n_db in ((100_000,) if quick else (100_000, 1_400_000)):
+        for F in (3, 13):
+            rs = np.random.RandomState(F)
+            vocab = ([17_000, 23_000, 49_000, 300, 40, 12] + [1000] * 7)[:F]
+            db = np.stack([rs.randint(0, v, size=n_db) for v in vocab], axis=1).astype(np.int64)
+            tables = retrieval.idf_tables(db)
+            db_t = torch.from_numpy(np.ascontiguousarray(db.astype(np.int32).T)).to(dev)
+            for Q in ((4, 256) if quick else (1, 4, 16, 64, 256, 4096)):
+                qry = np.stack([rs.randint(0, v, size=Q) for v in vocab], axis=1).astype(np.int64)
+                q_ids = torch.from_numpy(qry.astype(np.int32)).to(dev)
+                q_idf = torch.from_numpy(retrieval.map_data_to_idf(qry, tables)).to(dev)
+                out = (torch.empty((Q, K), dtype=torch.float64, device=dev), torch.empty((Q, K), dtype=torch.int64, device=dev),
+                       torch.empty((Q,), dtype=torch.int64, device=dev))
+
+                def parent():
+                    lib.call("rat_bm25_topk", *[ctypes.c_void_p(t.data_ptr()) for t in (db_t, q_ids, q_idf) + out], n_db, Q, F, K,
+                             ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                    return out
+                tiles = (Q + 3) // 4
+                variants = {"rat_bm25_topk": parent, "split(0)": lambda: ops.bm25_topk_split(db_t, q_ids, q_idf, K, splits=0, lib=lib)}
+                for s in SWEEP:
+                    if tiles * s <= 16384 and n_db // s >= 256:
+                        variants["split(%d)" % s] = (lambda s=s: ops.bm25_topk_split(db_t, q_ids, q_idf, K, splits=s, lib=lib))
+                want = tuple(t.clone() for t in parent())
+                torch.cuda.synchronize()
+                graphs = {}
+                for label, fn in variants.items():
+                    got = fn()
+                    torch.cuda.synchronize()
+                    for g, w in zip(got, want):
+                        assert torch.equal(g.view(torch.int64), w.view(torch.int64)), (n_db, F, Q, label)
+                    graphs[label], _ = _graph_of(fn, REPS)
+                ms = time_alternating(graphs, REPS, 50.0 if quick else MIN_TIMED_MS)
+                base = ms["rat_bm25_topk"]
+                ratio = ms["split(0)"] / base
+                worst_auto = max(worst_auto, ratio)
+                emit("N %8d  F %2d  Q %4d | %s | split(0) / rat_bm25_topk = %.3f (speed-up %.1fx)" %
+                     (n_db, F, Q, "  ".join("%s %.1f" % (k, v * 1e3) for k, v in ms.items()), ratio, base / ms["split(0)"]))
+                del graphs
+    emit("worst split(0) / rat_bm25_topk over the table: %.3f (the requirement: <= 1.02)" % worst_auto)
+
+
+def part2(emit, quick):
+    from rat_amd import synthetic
+    from rat_amd.model import RAT_m2
+    from rat_amd.online import OnlineScorer
+    name = "movielens_real_F3_K5_d10_B4096"
+    spec = synthetic.WORKLOADS[name]
+    fm = synthetic.feature_map_for(name, spec)
+    model = RAT_m2(fm, **synthetic.model_kwargs(spec, gpu=0))
+    model.eval()
+    n_pool = 100_000 if quick else 1_400_000
+    rs = np.random.RandomState(3)
+    vocab = [s["vocab_size"] for s in fm.feature_specs.values()]
+    pool = np.concatenate([np.stack([rs.randint(0, v, size=n_pool) for v in vocab], axis=1), rs.randint(0, 2, size=(n_pool, 1))], axis=1)
+    cfg = dict(topK=spec["K"], used_col_indices=list(range(spec["F"])), label_wise=False)
+    emit("== part 2: OnlineScorer.score() latency [us per request], %s, %d-row pool, host clock + synchronise" % (name, n_pool))
+    for B in (1, 16, 256):
+        ids = torch.from_numpy(np.stack([rs.randint(0, v, size=B) for v in vocab], axis=1).astype(np.int32)).to("cuda:0")
+        res = {}
+        for label, graph in (("eager", False), ("replayed", True)):
+            scorer = OnlineScorer(model, pool, cfg, graph=graph)
+            for _ in range(5):
+                y = scorer.score(ids)
+            torch.cuda.synchronize()
+            if graph:
+                assert any(e[1] for e in scorer._graphs.values()), "the request was not captured"
+            n, t0 = 0, time.perf_counter()
+            while time.perf_counter() - t0 < (0.1 if quick else 0.5):
+                y = scorer.score(ids)
+                torch.cuda.synchronize()
+                n += 1
+            res[label] = ((time.perf_counter() - t0) / n * 1e6, y)
+            del scorer
+        assert torch.equal(res["eager"][1], res["replayed"][1])
+        emit("B %4d | eager %.1f  replayed %.1f" % (B, res["eager"][0], res["replayed"][0]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None, help="also write the report to this file")
+    ap.add_argument("--quick", action="store_true", help="a few small points only (plumbing check)")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("online_bench.py measures on the GPU; no GPU is visible and there is no CPU fallback")
+    lines = []
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+    emit("tools/online_bench.py on %s, torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
+    part1(emit, args.quick)
+    part2(emit, args.quick)
+
+
+if __name__ == "__main__":
+    main()

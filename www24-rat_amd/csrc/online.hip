@@ -1,0 +1,410 @@
+// online.hip — the request path of the retrieval: ids of a fresh query batch -> neighbour lists, without leaving the device.
+//
+// The offline job (retrieval.hip, rat_bm25_topk) maps the query ids to IDF weights on the host (rat_amd/retrieval.py:
+// map_data_to_idf, a numpy searchsorted per column) and gives ONE work-group a tile of four queries and the whole pool — right for
+// 200 000 queries, wrong for a request of 1-64 rows, which would occupy 1-16 of the chip's 256 CUs.  Two pieces close that gap:
+//
+//   rat_bm25_query_prepare   map_data_to_idf on the device: a binary search per (query, column) in the pool's IDF tables (built
+//                            once per pool by retrieval.idf_tables and kept in HBM), including the reference's dtype rule — if
+//                            row 0 of the batch misses in a column, every weight of that column is truncated toward zero.
+//   rat_bm25_topk_split      rat_bm25_topk's contract with the pool cut into `splits` contiguous row ranges: work-group
+//                            (tile, range) scans its range exactly as bm25_topk_kernel scans the pool (same fp64 sums, f ascending)
+//                            and leaves its K best in workspace [Q][splits][K]; a second launch merges the partial lists of a query.
+//                            The order (score descending, pool index ascending) is total, and the K best of the pool are among
+//                            the K best of the ranges, so the result is the single-range result bit for bit, whatever `splits`.
+//
+// Both scan-side merges are per WAVE (lanes exchange their list heads through a wave-private LDS tile, no work-group barrier);
+// the four waves' lists of a work-group are then ranked against each other after the one barrier of the kernel.
+// Nothing here allocates, synchronises or uses a floating-point atomic: the pair is captured into the serving graph (rat_amd/online.py).
+#include "rat_device.h"
+#include "../../include/rat_hip.h"
+
+namespace {
+
+constexpr int ON_THREADS = 256;
+constexpr int ON_WAVES = ON_THREADS / 64;
+constexpr int ON_FMAX = 32;
+constexpr int ON_KMAX = 32;
+constexpr int ON_MAX_SPLITS = 4096;
+// splits = 0: the rule read off tools/online_bench.py's sweep (profiles/online/online_bench.txt): with at least one query
+// tile per CU the single-range kernel already fills the chip; below that, enough ranges for ON_TARGET_GROUPS work-groups (two per
+// CU — what the scan kernel's 226 VGPRs let a CU hold; more ranges only add merge work), every range at least one full trip of the
+// scan loop (256 lanes x 4 rows), at most ON_AUTO_MAX_SPLITS.
+constexpr int64_t ON_SINGLE_TILES = 256;
+constexpr int64_t ON_TARGET_GROUPS = 512;
+constexpr int64_t ON_MIN_RANGE_ROWS = 1024;
+constexpr int64_t ON_AUTO_MAX_SPLITS = 256;
+
+__device__ __forceinline__ bool better(double sa, int64_t ia, double sb, int64_t ib) {   // (score desc, index asc)
+    return sa > sb || (sa == sb && ia < ib);
+}
+// candidate (so, io) against the running best (cs, ci); an index < 0 is "no entry"
+__device__ __forceinline__ void take_better(double so, int64_t io, double& cs, int64_t& ci) {
+    if (io >= 0 && (ci < 0 || better(so, io, cs, ci))) {
+        cs = so;
+        ci = io;
+    }
+}
+
+// ---- arg-max over the 64 lanes of ONE wave, QT independent problems at once: every lane passes a candidate per problem and gets
+// the wave's best back.  Two levels through a wave-private LDS tile (64 heads -> 8 group bests -> 1), double-buffered by the
+// call's parity so that a call costs two wave fences and no work-group barrier.
+template <int QT>
+struct WaveTile {
+    double hv[2][QT][64];
+    int64_t hi[2][QT][64];
+    double gv[2][QT][8];
+    int64_t gi[2][QT][8];
+};
+
+template <int QT>
+__device__ __forceinline__ void wave_best(WaveTile<QT>& w, int parity, double (&s)[QT], int64_t (&i)[QT]) {
+    const int lane = rat_lane();
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+        w.hv[parity][t][lane] = s[t];
+        w.hi[parity][t][lane] = i[t];
+    }
+    RAT_WAVE_FENCE();
+    const int g = lane & 7;
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+        double cs = 0.0;
+        int64_t ci = -1;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) take_better(w.hv[parity][t][8 * g + j], w.hi[parity][t][8 * g + j], cs, ci);
+        if (lane < 8) {
+            w.gv[parity][t][g] = cs;
+            w.gi[parity][t][g] = ci;
+        }
+    }
+    RAT_WAVE_FENCE();
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+        double cs = 0.0;
+        int64_t ci = -1;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) take_better(w.gv[parity][t][j], w.gi[parity][t][j], cs, ci);
+        s[t] = cs;
+        i[t] = ci;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ pass 1: scan a range
+struct SplitArgs {
+    const int32_t* db_t;     // [F][N]
+    const int32_t* qry;      // [Q][F]
+    const double* idf;       // [Q][F]
+    double* part_val;        // [Q][splits][K]
+    int64_t* part_idx;       // [Q][splits][K]
+    double* out_val;         // [Q][K]
+    int64_t* out_idx;        // [Q][K]
+    int64_t* out_len;        // [Q]
+    int64_t N, Q;
+    int F, K, splits;
+};
+
+template <int KMAX, int QT, int RU>
+__global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a) {
+    __shared__ WaveTile<QT> tile_s[ON_WAVES];
+    __shared__ double wl_v[ON_WAVES][QT][KMAX];          // the K best of every wave, ranked against each other after the barrier
+    __shared__ int64_t wl_i[ON_WAVES][QT][KMAX];
+    const int tid = threadIdx.x, lane = rat_lane(), wave = rat_wave();
+    const int64_t ntiles = (a.Q + QT - 1) / QT;
+    const int64_t chunk = (a.N + a.splits - 1) / a.splits;
+    int parity = 0;
+    for (int64_t item = blockIdx.x; item < ntiles * a.splits; item += gridDim.x) {
+        const int64_t q0 = (item / a.splits) * QT;
+        const int split = (int)(item % a.splits);
+        const int64_t lo = split * chunk < a.N ? split * chunk : a.N;        // ranges past the end of the pool are empty
+        const int64_t hi = lo + chunk < a.N ? lo + chunk : a.N;
+        double val[QT][KMAX], kth[QT];                     // kth = score of the current K-th entry (0 while the list is not full)
+        int64_t idx[QT][KMAX];
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {
+            kth[t] = 0.0;
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k) {
+                val[t][k] = 0.0;
+                idx[t][k] = -1;
+            }
+        }
+        // ---- scan rows [lo, hi) the way bm25_topk_kernel scans [0, N): every lane walks its rows in increasing order, so among
+        //      equal scores the lower index arrives first and a later row must be STRICTLY better than the K-th entry to get in
+        for (int64_t n0 = lo + tid; n0 < hi; n0 += (int64_t)ON_THREADS * RU) {
+            double s[RU][QT];
+#pragma unroll
+            for (int u = 0; u < RU; ++u)
+#pragma unroll
+                for (int t = 0; t < QT; ++t) s[u][t] = 0.0;
+            for (int f = 0; f < a.F; ++f) {
+                int32_t id[RU];
+#pragma unroll
+                for (int u = 0; u < RU; ++u) {                                            // RU independent loads in flight per field
+                    const int64_t n = n0 + (int64_t)u * ON_THREADS;
+                    id[u] = n < hi ? a.db_t[(int64_t)f * a.N + n] : -1;
+                }
+#pragma unroll
+                for (int t = 0; t < QT; ++t) {
+                    const int64_t q = q0 + t < a.Q ? q0 + t : a.Q - 1;                    // wave-uniform: scalar loads
+                    const int32_t qid = a.qry[q * a.F + f];
+                    const double w = a.idf[q * a.F + f];
+#pragma unroll
+                    for (int u = 0; u < RU; ++u) s[u][t] += (qid == id[u] && n0 + (int64_t)u * ON_THREADS < hi) ? w : 0.0;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < RU; ++u) {                                                // rows in increasing order
+                const int64_t n = n0 + (int64_t)u * ON_THREADS;
+#pragma unroll
+                for (int t = 0; t < QT; ++t) {
+                    if (s[u][t] > kth[t]) {                                               // positive AND strictly better than the K-th
+                        double cs = s[u][t];
+                        int64_t ci = n;
+                        bool placed = false;          // once the newcomer sits the rest only shifts down (see bm25_topk_kernel)
+#pragma unroll
+                        for (int k = 0; k < KMAX; ++k) {
+                            if (k < a.K && (placed || cs > val[t][k])) {
+                                placed = true;
+                                const double ts = val[t][k];
+                                const int64_t ti = idx[t][k];
+                                val[t][k] = cs;
+                                idx[t][k] = ci;
+                                cs = ts;
+                                ci = ti;
+                            }
+                            if (k == a.K - 1) kth[t] = val[t][k];
+                        }
+                    }
+                }
+            }
+        }
+        // ---- every wave merges its 64 private lists: up to K rounds of a wave arg-max over the lists' heads, the QT queries in
+        //      lock step.  Lane t * KMAX + k keeps slot (t, k) of the wave's result.  A wave none of whose lanes owns a row
+        //      (wave-uniform) has nothing to merge.
+        int k_end = 0;
+        if (lo + (int64_t)wave * 64 < hi) {
+            for (; k_end < a.K; ++k_end) {
+                double hs[QT];
+                int64_t hx[QT];
+#pragma unroll
+                for (int t = 0; t < QT; ++t) {
+                    hs[t] = val[t][0];
+                    hx[t] = idx[t][0];
+                }
+                wave_best<QT>(tile_s[wave], parity, hs, hx);
+                parity ^= 1;
+                bool any = false;
+#pragma unroll
+                for (int t = 0; t < QT; ++t) {
+                    any |= hx[t] >= 0;
+                    if (hx[t] >= 0 && idx[t][0] == hx[t]) {                                // the winner pops its head
+#pragma unroll
+                        for (int j = 0; j + 1 < KMAX; ++j) {
+                            val[t][j] = val[t][j + 1];
+                            idx[t][j] = idx[t][j + 1];
+                        }
+                        val[t][KMAX - 1] = 0.0;
+                        idx[t][KMAX - 1] = -1;
+                    }
+                    if (lane == t * KMAX + k_end) {
+                        wl_v[wave][t][k_end] = hx[t] >= 0 ? hs[t] : 0.0;
+                        wl_i[wave][t][k_end] = hx[t];
+                    }
+                }
+                if (!any) {                            // every list of every query is exhausted (the same in all lanes)
+                    ++k_end;
+                    break;
+                }
+            }
+        }
+        if (lane < QT * KMAX && lane % KMAX >= k_end) {
+            wl_v[wave][lane / KMAX][lane % KMAX] = 0.0;
+            wl_i[wave][lane / KMAX][lane % KMAX] = -1;
+        }
+        __syncthreads();
+        // ---- rank the four waves' lists against each other: entry (w, t, k) goes to slot (number of better entries), if < K
+        if (tid < ON_WAVES * QT * KMAX) {
+            const int w = tid / (QT * KMAX), t = (tid / KMAX) % QT, k = tid % KMAX;
+            if (k < a.K && q0 + t < a.Q) {
+                const double es = wl_v[w][t][k];
+                const int64_t ei = wl_i[w][t][k];
+                int rank = 0, total = 0;
+                for (int w2 = 0; w2 < ON_WAVES; ++w2)
+                    for (int k2 = 0; k2 < a.K; ++k2) {
+                        const int64_t oi = wl_i[w2][t][k2];
+                        total += oi >= 0 ? 1 : 0;
+                        rank += (oi >= 0 && ei >= 0 && better(wl_v[w2][t][k2], oi, es, ei)) ? 1 : 0;
+                    }
+                const int64_t base = ((q0 + t) * a.splits + split) * a.K;
+                if (ei >= 0 && rank < a.K) {
+                    a.part_val[base + rank] = es;
+                    a.part_idx[base + rank] = ei;
+                }
+                if (w == 0 && k >= total) {                                                // fewer than K candidates in this range
+                    a.part_val[base + k] = 0.0;
+                    a.part_idx[base + k] = -1;
+                }
+            }
+        }
+        __syncthreads();                               // the next item reuses wl_*
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ pass 2: merge
+// One wave per query over its splits * K partial entries: round k picks the best entry that comes AFTER round k - 1's winner in the
+// total order (indices are distinct, so "after" is strict) — no per-list state.
+__global__ void __launch_bounds__(64) bm25_merge_kernel(SplitArgs a) {
+    __shared__ WaveTile<1> tile_s;
+    const int lane = rat_lane();
+    const int64_t C = (int64_t)a.splits * a.K;
+    int parity = 0;
+    for (int64_t q = blockIdx.x; q < a.Q; q += gridDim.x) {
+        const double* pv = a.part_val + q * C;
+        const int64_t* pi = a.part_idx + q * C;
+        double ps = 0.0;
+        int64_t px = -1;                               // previous winner (none yet)
+        int k = 0;
+        for (; k < a.K; ++k) {
+            double cs[1] = {0.0};
+            int64_t ci[1] = {-1};
+            for (int64_t c = lane; c < C; c += 64) {
+                const double s = pv[c];
+                const int64_t i = pi[c];
+                if (i >= 0 && (px < 0 || better(ps, px, s, i))) take_better(s, i, cs[0], ci[0]);
+            }
+            wave_best<1>(tile_s, parity, cs, ci);
+            parity ^= 1;
+            if (ci[0] < 0) break;                      // nothing left (the same in all lanes)
+            ps = cs[0];
+            px = ci[0];
+            if (lane == 0) {
+                a.out_val[q * a.K + k] = ps;
+                a.out_idx[q * a.K + k] = px;
+            }
+        }
+        for (int j = k + lane; j < a.K; j += 64) {     // zero scores are dropped: index -1, value 0
+            a.out_val[q * a.K + j] = 0.0;
+            a.out_idx[q * a.K + j] = -1;
+        }
+        if (lane == 0) a.out_len[q] = k;
+    }
+}
+
+int64_t auto_splits(int64_t n_qry, int64_t n_db, int topk) {
+    const int64_t tiles = topk <= 8 ? (n_qry + 3) / 4 : n_qry;
+    if (tiles >= ON_SINGLE_TILES) return 1;
+    int64_t s = (ON_TARGET_GROUPS + tiles - 1) / tiles;
+    const int64_t by_rows = n_db / ON_MIN_RANGE_ROWS;
+    if (s > by_rows) s = by_rows;
+    if (s > ON_AUTO_MAX_SPLITS) s = ON_AUTO_MAX_SPLITS;
+    return s < 1 ? 1 : s;
+}
+
+// ------------------------------------------------------------------------------------------------------------ query-side IDF mapping
+struct PrepArgs {
+    const int32_t* ids;      // [Q][row_stride]
+    const int32_t* cols;     // [F]
+    const int32_t* tab_ids;  // per column: sorted distinct ids, concatenated
+    const double* tab_idf;   // their weights
+    const int64_t* tab_off;  // [F + 1]
+    int32_t* qry_ids;        // [Q][F]
+    double* qry_idf;         // [Q][F]
+    int64_t Q;
+    int row_stride, F;
+};
+
+// np.searchsorted(vals, x) clipped to the last entry, then vals[pos] == x (retrieval.map_data_to_idf): -> position or -1
+__device__ __forceinline__ int64_t table_find(const int32_t* vals, int64_t n, int32_t x) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (vals[mid] < x)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo < n && vals[lo] == x ? lo : -1;
+}
+
+__global__ void __launch_bounds__(256) bm25_query_prepare_kernel(PrepArgs a) {
+    const int64_t total = a.Q * a.F;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t q = e / a.F;
+        const int f = (int)(e % a.F);
+        const int32_t* vals = a.tab_ids + a.tab_off[f];
+        const double* idf = a.tab_idf + a.tab_off[f];
+        const int64_t n = a.tab_off[f + 1] - a.tab_off[f];
+        const int32_t x = a.ids[q * a.row_stride + a.cols[f]];
+        const int64_t pos = table_find(vals, n, x);
+        double w = pos >= 0 ? idf[pos] : 0.0;
+        // the reference's np.vectorize takes the column's dtype from the batch's FIRST row: a miss there makes the column int64
+        if (table_find(vals, n, a.ids[a.cols[f]]) < 0) w = (double)(int64_t)w;
+        a.qry_ids[e] = x;
+        a.qry_idf[e] = w;
+    }
+}
+
+}  // namespace
+
+extern "C" int rat_bm25_query_prepare(const int32_t* ids, const int32_t* cols, const int32_t* table_ids, const double* table_idf,
+                                      const int64_t* table_offsets, int32_t* qry_ids, double* qry_idf, int64_t n_qry, int row_stride,
+                                      int n_fields, void* stream) {
+    RAT_REQUIRE(ids && cols && table_ids && table_idf && table_offsets && qry_ids && qry_idf, "null pointer");
+    RAT_REQUIRE(n_qry > 0 && n_fields > 0 && row_stride > 0, "bad dims");
+    RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
+    PrepArgs a{ids, cols, table_ids, table_idf, table_offsets, qry_ids, qry_idf, n_qry, row_stride, n_fields};
+    const int64_t blocks = (n_qry * n_fields + 255) / 256;
+    RAT_LAUNCH(bm25_query_prepare_kernel, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
+    return rat_check_launch("rat_bm25_query_prepare");
+}
+
+extern "C" size_t rat_bm25_topk_split_workspace(int64_t n_qry, int topk, int splits) {
+    if (n_qry <= 0 || topk <= 0 || splits < 0) return 0;
+    // splits = 0: the most the library may choose for this many queries (it does not know the pool yet)
+    const int64_t s = splits > 0 ? splits : auto_splits(n_qry, INT64_MAX, topk);
+    return (size_t)n_qry * (size_t)s * (size_t)topk * (sizeof(double) + sizeof(int64_t));
+}
+
+extern "C" int rat_bm25_topk_split(const int32_t* db_ids_field_major, const int32_t* qry_ids, const double* qry_idf, double* out_values,
+                                   int64_t* out_indices, int64_t* out_lens, void* workspace, size_t workspace_bytes, int64_t n_db,
+                                   int64_t n_qry, int n_fields, int topk, int splits, void* stream) {
+    RAT_REQUIRE(db_ids_field_major && qry_ids && qry_idf && out_values && out_indices && out_lens, "null pointer");
+    RAT_REQUIRE(n_db > 0 && n_qry > 0 && n_fields > 0 && topk > 0, "bad dims");
+    RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
+    RAT_REQUIRE(topk <= ON_KMAX, "topK > 32 is not supported");
+    RAT_REQUIRE(splits >= 0 && splits <= ON_MAX_SPLITS, "splits must be 0 (library's choice) or 1..4096");
+    if (splits == 0) {
+        splits = (int)auto_splits(n_qry, n_db, topk);
+        if (splits == 1)                               // the query tiles fill the chip: the single-range kernel, no second pass
+            return rat_bm25_topk(db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, n_db, n_qry, n_fields, topk,
+                                 stream);
+    }
+    const size_t need = (size_t)n_qry * (size_t)splits * (size_t)topk * (sizeof(double) + sizeof(int64_t));
+    RAT_REQUIRE(workspace != nullptr && workspace_bytes >= need, "workspace smaller than rat_bm25_topk_split_workspace()");
+    RAT_REQUIRE(((uintptr_t)workspace & 7) == 0, "workspace must be 8-byte aligned");
+    SplitArgs a{};
+    a.db_t = db_ids_field_major;
+    a.qry = qry_ids;
+    a.idf = qry_idf;
+    a.part_val = static_cast<double*>(workspace);
+    a.part_idx = reinterpret_cast<int64_t*>(a.part_val + (size_t)n_qry * splits * topk);
+    a.out_val = out_values;
+    a.out_idx = out_indices;
+    a.out_len = out_lens;
+    a.N = n_db;
+    a.Q = n_qry;
+    a.F = n_fields;
+    a.K = topk;
+    a.splits = splits;
+    if (topk <= 8) {
+        const int64_t items = (n_qry + 3) / 4 * splits;
+        RAT_LAUNCH((bm25_scan_split_kernel<8, 4, 4>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
+    } else {
+        const int64_t items = n_qry * splits;
+        RAT_LAUNCH((bm25_scan_split_kernel<32, 1, 4>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
+    }
+    if (rat_check_launch("rat_bm25_topk_split") != 0) return -1;
+    RAT_LAUNCH(bm25_merge_kernel, (unsigned)(n_qry < 65536 ? n_qry : 65536), 64, 0, stream, a);
+    return rat_check_launch("rat_bm25_topk_split");
+}

@@ -151,6 +151,10 @@ _SIGNATURES = {
     "rat_logit_bwd_pool": (c_int, [_P, _P, _P, c_int64, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int, _P, c_int64, c_float, _P, c_int,
                                    c_int, c_int, _P]),
     "rat_sparse_reduce_scalar_pool": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
+    # the request path (rat_amd/online.py): query-side IDF mapping and the top-K scan split over pool ranges
+    "rat_bm25_query_prepare": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, _P]),
+    "rat_bm25_topk_split_workspace": (c_size_t, [c_int64, c_int, c_int]),
+    "rat_bm25_topk_split": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_size_t, c_int64, c_int64, c_int, c_int, c_int, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

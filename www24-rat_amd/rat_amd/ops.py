@@ -925,3 +925,39 @@ def owner_scatter(dense_a, dense_b, extra_out, lists, stride, world, cap_a, cap_
     _chk(lists, name="lists")
     lib.call("rat_owner_scatter", _p(dense_a), _p(dense_b), _p(extra_out), _p(lists), int(stride), int(world), int(cap_a), int(cap_b),
              int(d), int(n_extra), _stream(lists))
+
+
+# ----------------------------------------------------------------------------- K6b: the request path (rat_amd/online.py)
+def bm25_query_prepare(ids, cols, table_ids, table_idf, table_offsets, lib=None):
+    """ids int32 [Q, L] (full encoded rows) -> (qry_ids int32 [Q, F], qry_idf fp64 [Q, F]): retrieval.map_data_to_idf of ONE query
+    batch against the pool's IDF tables (flat: sorted ids int32, weights fp64, offsets int64 [F + 1]), all on the device"""
+    lib = lib or get_lib()
+    _chk(ids, torch.int32, "ids"), _chk(cols, torch.int32, "cols"), _chk(table_ids, torch.int32, "table_ids")
+    _chk(table_idf, torch.float64, "table_idf"), _chk(table_offsets, torch.int64, "table_offsets")
+    Q, L = ids.shape
+    F = cols.numel()
+    assert table_offsets.numel() == F + 1
+    qry_ids = torch.empty((Q, F), dtype=torch.int32, device=ids.device)
+    qry_idf = torch.empty((Q, F), dtype=torch.float64, device=ids.device)
+    lib.call("rat_bm25_query_prepare", _p(ids), _p(cols), _p(table_ids), _p(table_idf), _p(table_offsets), _p(qry_ids), _p(qry_idf),
+             Q, L, F, _stream(ids))
+    return qry_ids, qry_idf
+
+
+def bm25_topk_split(db_t, qry_ids, qry_idf, topk, splits=0, lib=None):
+    """rat_bm25_topk over `splits` pool ranges (0: the library chooses) -> (values fp64 [Q, K], indices int64 [Q, K], lens int64 [Q]);
+    db_t int32 [F, N] field-major"""
+    lib = lib or get_lib()
+    _chk(db_t, torch.int32, "db_t"), _chk(qry_ids, torch.int32, "qry_ids"), _chk(qry_idf, torch.float64, "qry_idf")
+    F, N = db_t.shape
+    Q = qry_ids.shape[0]
+    assert tuple(qry_ids.shape) == (Q, F) and tuple(qry_idf.shape) == (Q, F)
+    dev = db_t.device
+    nbytes = lib.size("rat_bm25_topk_split_workspace", Q, int(topk), int(splits))
+    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    out_v = torch.empty((Q, topk), dtype=torch.float64, device=dev)
+    out_i = torch.empty((Q, topk), dtype=torch.int64, device=dev)
+    out_l = torch.empty((Q,), dtype=torch.int64, device=dev)
+    lib.call("rat_bm25_topk_split", _p(db_t), _p(qry_ids), _p(qry_idf), _p(out_v), _p(out_i), _p(out_l), _p(ws), ws.numel() * 8, N, Q, F,
+             int(topk), int(splits), _stream(db_t))
+    return out_v, out_i, out_l
