@@ -355,6 +355,32 @@ int rat_bm25_topk_split(const int32_t* db_ids_field_major, const int32_t* qry_id
                         int64_t* out_indices, int64_t* out_lens, void* workspace, size_t workspace_bytes, int64_t n_db,
                         int64_t n_qry, int n_fields, int topk, int splits, void* stream);
 
+/* ---- K6c: a pool that grows in place (online scoring with reserved capacity; additive in ABI v9) -------------------
+ * The pool's buffers are allocated for `capacity` rows once — db_ids_field_major [n_fields][capacity], pool_ids [capacity][row_len],
+ * pool_labels [capacity] — and the number of rows that count lives in DEVICE memory (n_db_dev, one int64), so that launches captured
+ * into a hipGraph before an append serve the grown pool after it: no kernel argument depends on the row count.
+ *
+ * rat_pool_append: n = *n_db_dev; rows i < n_rows of ids [n_rows][row_len] int32 / labels [n_rows] fp32 (device) are written to
+ * pool_ids[n + i][:], pool_labels[n + i] and, transposed, db_ids_field_major[f][n + i] = ids[i][cols[f]] (64 consecutive rows of a
+ * column per wave); a one-thread tail launch then sets *n_db_dev = n + n_rows.  Both read n on the device: appends queue back to back
+ * without a synchronisation.  n + n_rows > capacity writes nothing and leaves the count (the caller checks beforehand).  pool_ids and
+ * pool_labels may both be NULL (an index without the row store; labels is then ignored).  Append-only: rows are never removed. */
+int rat_pool_append(const int32_t* ids, const float* labels, const int32_t* cols, int32_t* db_ids_field_major, int32_t* pool_ids,
+                    float* pool_labels, int64_t* n_db_dev, int64_t n_rows, int64_t capacity, int row_len, int n_fields, void* stream);
+/* rat_bm25_topk_split over the first *n_db_dev rows of a [n_fields][capacity] pool.  splits = 0: rat_bm25_topk_split's rule applied
+ * to the CAPACITY (the launch shape never changes); where that rule hands over to rat_bm25_topk, the same scan runs with one range
+ * here.  Range r covers rows [r c, min((r + 1) c, n)) with c = ceil(n / splits) of the CURRENT n; rows >= n are never read.  The scan
+ * and merge code is rat_bm25_topk_split's, so the result equals rat_bm25_topk over the first n rows bit for bit.  Workspace as there
+ * (always needed). */
+int rat_bm25_topk_split_dev(const int32_t* db_ids_field_major, const int64_t* n_db_dev, const int32_t* qry_ids, const double* qry_idf,
+                            double* out_values, int64_t* out_indices, int64_t* out_lens, void* workspace, size_t workspace_bytes,
+                            int64_t capacity, int64_t n_qry, int n_fields, int topk, int splits, void* stream);
+/* rat_batch_assemble with the pool's row count N read from *n_pool_dev: a negative neighbour index (the -1 padding of a short list)
+ * counts back from the pool's last LIVE row, which moves with every append. */
+int rat_batch_assemble_dev(const int32_t* data_ids, const float* data_labels, const int32_t* pool_ids, const float* pool_labels,
+                           const int64_t* retr_indices, const int64_t* rows, int32_t* idx, int32_t* label_ids, float* y_true,
+                           int64_t Q, const int64_t* n_pool_dev, int B, int K, int L, void* stream);
+
 /* ---- K3: prediction head -----------------------------------------------------------------------------
  * Plain fp32 GEMM on MFMA for MLP_Layer's nn.Linear (deep.py:126-141) forward / dgrad / wgrad:
  * C[M][N] = op(A) op(B) (+ bias[N]) (+ beta*C), row-major with leading dimensions, op = transpose flag. */

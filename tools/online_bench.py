@@ -10,6 +10,11 @@ before anything is timed.  Every variant is captured as a hipGraph of REPS back-
 events (warm-up replays first, at least 0.5 s of timed work per point), so a figure is device time per call, free of launch issue.
 Part 2 — latency of OnlineScorer.score() (retrieve -> assemble -> eval forward), eager and replayed, at B in {1, 16, 256} for the
 MovieLens-real geometry (movielens_real_F3_K5_d10_B4096's model, 1.4 M-row synthetic pool): host clock around score() + synchronise.
+--append — the growing pool instead (profiles/online/append_bench.txt): (i) OnlineScorer-independent cost of taking rows in,
+RetrievalIndex.append(M rows) on an index with reserved capacity against the only way an immutable index has — a new RetrievalIndex
+over np.concatenate([pool, rows]) — for M in {1, 64, 4096}; (ii) replayed score() latency of a scorer with capacity (1.4 M rows in
+room for 2 M) against the immutable scorer over the same pool at B in {1, 16, 256}.  Host clock around a synchronise, the two sides
+alternating round by round in one process, at least 0.5 s of timed work per point and side; mean, and min .. max over the rounds.
 There is no CPU fallback: without a GPU the tool exits with an error."""
 import argparse
 import os
@@ -150,10 +155,102 @@ def part2(emit, quick):
         emit("B %4d | eager %.1f  replayed %.1f" % (B, res["eager"][0], res["replayed"][0]))
 
 
+def _movielens(quick):
+    from rat_amd import synthetic
+    from rat_amd.model import RAT_m2
+    name = "movielens_real_F3_K5_d10_B4096"
+    spec = synthetic.WORKLOADS[name]
+    fm = synthetic.feature_map_for(name, spec)
+    model = RAT_m2(fm, **synthetic.model_kwargs(spec, gpu=0))
+    model.eval()
+    n_pool, capacity = (100_000, 150_000) if quick else (1_400_000, 2_000_000)
+    rs = np.random.RandomState(3)
+    vocab = [s["vocab_size"] for s in fm.feature_specs.values()]
+
+    def rows(n):
+        return np.concatenate([np.stack([rs.randint(0, v, size=n) for v in vocab], axis=1), rs.randint(0, 2, size=(n, 1))], axis=1)
+    cfg = dict(topK=spec["K"], used_col_indices=list(range(spec["F"])), label_wise=False)
+    return name, model, rows, vocab, cfg, n_pool, capacity
+
+
+def _stats(xs):
+    return "%.1f (%.1f .. %.1f, %d rounds)" % (sum(xs) / len(xs), min(xs), max(xs), len(xs))
+
+
+def part_append(emit, quick):
+    from rat_amd.online import OnlineScorer, RetrievalIndex
+    name, model, rows, vocab, cfg, n_pool, capacity = _movielens(quick)
+    dev, K, cols = torch.device("cuda:0"), cfg["topK"], cfg["used_col_indices"]
+    min_s = 0.05 if quick else MIN_TIMED_MS / 1e3
+    pool = rows(n_pool)
+    emit("== append (i): taking M labelled rows into a %d-row pool (%s columns), capacity %d [ms per call]: RetrievalIndex.append "
+         "against a new RetrievalIndex over np.concatenate([pool, rows]) (concatenate included); host clock + synchronise, alternating"
+         % (n_pool, len(cols), capacity))
+    index = RetrievalIndex(pool, cols, K, dev, capacity=capacity)
+    cur = pool
+    for M in (1, 64, 4096):
+        t_app, t_new = [], []
+        while sum(t_app) < min_s or sum(t_new) < min_s or len(t_app) < 3 or len(t_new) < 3:
+            new = rows(M)
+            appended = (sum(t_app) < min_s or len(t_app) < 3) and len(index) + M <= capacity
+            if appended:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                index.append(new)
+                torch.cuda.synchronize()
+                t_app.append((time.perf_counter() - t0) * 1e3)
+            if sum(t_new) < min_s or len(t_new) < 3:     # the same rows into the same pool, the immutable way
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fresh = RetrievalIndex(np.concatenate([cur, new]), cols, K, dev)
+                torch.cuda.synchronize()
+                t_new.append((time.perf_counter() - t0) * 1e3)
+                del fresh
+            elif not appended:
+                break
+            if appended:
+                cur = np.concatenate([cur, new])
+        a, b = sum(t_app) / len(t_app), sum(t_new) / len(t_new)
+        emit("M %5d | append %s | new index %s | append / new index = %.5f (%.0fx)" % (M, _stats(t_app), _stats(t_new), a / b, b / a))
+    # the appended index still answers like a fresh one over the same rows
+    ids = torch.from_numpy(np.stack([np.random.RandomState(9).randint(0, v, size=16) for v in vocab], axis=1).astype(np.int32)).to(dev)
+    fresh = RetrievalIndex(cur, cols, K, dev)
+    for g, w in zip(index.retrieve(ids), fresh.retrieve(ids)):
+        assert torch.equal(g.view(torch.int64), w.view(torch.int64)), "appended index != fresh index"
+    emit("   (after %d appended rows retrieve() equals a fresh index over the same rows, bit for bit)" % (len(index) - n_pool))
+    del index, fresh
+
+    emit("== append (ii): replayed OnlineScorer.score() [us per request], %s, %d-row pool: capacity = %d against the immutable scorer; "
+         "host clock + synchronise, rounds of %d requests alternating" % (name, n_pool, capacity, 200))
+    grow = OnlineScorer(model, pool, cfg, graph=True, capacity=capacity)
+    fixed = OnlineScorer(model, pool, cfg, graph=True)
+    rs = np.random.RandomState(5)
+    for B in (1, 16, 256):
+        ids = torch.from_numpy(np.stack([rs.randint(0, v, size=B) for v in vocab], axis=1).astype(np.int32)).to(dev)
+        for sc in (grow, fixed):
+            for _ in range(5):
+                y = sc.score(ids)
+            torch.cuda.synchronize()
+            assert any(e[1] for e in sc._graphs.values()), "the request was not captured"
+        assert torch.equal(grow.score(ids), fixed.score(ids))
+        per = {"capacity": [], "immutable": []}
+        while min(sum(v) for v in per.values()) * 200 / 1e6 < min_s:
+            for label, sc in (("capacity", grow), ("immutable", fixed)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(200):
+                    sc.score(ids)
+                    torch.cuda.synchronize()
+                per[label].append((time.perf_counter() - t0) / 200 * 1e6)
+        a, b = (sum(per[k]) / len(per[k]) for k in ("capacity", "immutable"))
+        emit("B %4d | capacity %s | immutable %s | capacity / immutable = %.4f" % (B, _stats(per["capacity"]), _stats(per["immutable"]), a / b))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the report to this file")
     ap.add_argument("--quick", action="store_true", help="a few small points only (plumbing check)")
+    ap.add_argument("--append", action="store_true", help="measure the growing pool (append against a new index; replay with capacity)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("online_bench.py measures on the GPU; no GPU is visible and there is no CPU fallback")
@@ -167,6 +264,9 @@ def main():
             with open(args.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
     emit("tools/online_bench.py on %s, torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
+    if args.append:
+        part_append(emit, args.quick)
+        return
     part1(emit, args.quick)
     part2(emit, args.quick)
 

@@ -28,12 +28,17 @@ struct BatchArgs {
     float* y_true;
     int64_t Q, N;
     int B, K, L;
+    const int64_t* n_dev;    // DEV only: the pool's row count in device memory (N is then not used)
 };
 
 // one thread per output id: consecutive threads write consecutive ints of idx (coalesced); the source rows are L ints
 // (80 bytes at the north-star config) fetched by L neighbouring lanes
+// DEV: the pool's row count — what a negative neighbour index counts back from — is read from device memory: the pool of an online
+// index with reserved capacity grows under a captured request, and -1 must keep resolving to its last LIVE row
+template <bool DEV>
 __global__ void __launch_bounds__(256) batch_assemble_kernel(BatchArgs a) {
     const int T = a.K + 1;
+    const int64_t N = DEV ? *a.n_dev : a.N;
     const int64_t total = (int64_t)a.B * T * a.L;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
         const int c = (int)(e % a.L);
@@ -50,7 +55,7 @@ __global__ void __launch_bounds__(256) batch_assemble_kernel(BatchArgs a) {
             }
         } else {
             int64_t nb = a.retr_indices[row * a.K + (t - 1)];
-            if (nb < 0) nb += a.N;
+            if (nb < 0) nb += N;
             v = a.pool_ids[nb * a.L + c];
             if (c == 0) a.label_ids[bt] = (int32_t)a.pool_labels[nb];
         }
@@ -66,11 +71,25 @@ extern "C" int rat_batch_assemble(const int32_t* data_ids, const float* data_lab
     RAT_REQUIRE(data_ids && data_labels && pool_ids && pool_labels && rows && idx && label_ids && y_true, "null pointer");
     RAT_REQUIRE(K == 0 || retr_indices != nullptr, "null retr_indices");
     RAT_REQUIRE(B > 0 && K >= 0 && L > 0 && Q > 0 && N > 0, "bad dims");
-    BatchArgs a{data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, idx, label_ids, y_true, Q, N, B, K, L};
+    BatchArgs a{data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, idx, label_ids, y_true, Q, N, B, K, L, nullptr};
     const int64_t total = (int64_t)B * (K + 1) * L;
     const int64_t blocks = (total + 255) / 256;
-    RAT_LAUNCH(batch_assemble_kernel, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
+    RAT_LAUNCH(batch_assemble_kernel<false>, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
     return rat_check_launch("rat_batch_assemble");
+}
+
+extern "C" int rat_batch_assemble_dev(const int32_t* data_ids, const float* data_labels, const int32_t* pool_ids,
+                                      const float* pool_labels, const int64_t* retr_indices, const int64_t* rows, int32_t* idx,
+                                      int32_t* label_ids, float* y_true, int64_t Q, const int64_t* n_pool_dev, int B, int K, int L,
+                                      void* stream) {
+    RAT_REQUIRE(data_ids && data_labels && pool_ids && pool_labels && rows && idx && label_ids && y_true && n_pool_dev, "null pointer");
+    RAT_REQUIRE(K == 0 || retr_indices != nullptr, "null retr_indices");
+    RAT_REQUIRE(B > 0 && K >= 0 && L > 0 && Q > 0, "bad dims");
+    BatchArgs a{data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, idx, label_ids, y_true, Q, 0, B, K, L, n_pool_dev};
+    const int64_t total = (int64_t)B * (K + 1) * L;
+    const int64_t blocks = (total + 255) / 256;
+    RAT_LAUNCH(batch_assemble_kernel<true>, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
+    return rat_check_launch("rat_batch_assemble_dev");
 }
 
 // ---- inputs_to_device + the label-token rule for a batch that is ALREADY on the device (ABI v8) --------------------------------------

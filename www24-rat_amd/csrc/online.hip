@@ -100,24 +100,35 @@ struct SplitArgs {
     double* out_val;         // [Q][K]
     int64_t* out_idx;        // [Q][K]
     int64_t* out_len;        // [Q]
-    int64_t N, Q;
+    int64_t N, Q;            // N: rows of the pool — DEV: read from *n_dev instead, and N is not used
     int F, K, splits;
+    const int64_t* n_dev;    // DEV only: the pool's current row count (the header a RetrievalIndex with capacity keeps)
+    int64_t stride;          // DEV only: column stride of db_t (the capacity); otherwise the stride is N
 };
 
-template <int KMAX, int QT, int RU>
+// DEV = false: rat_bm25_topk_split (row count and column stride are the host argument N).  DEV = true: rat_bm25_topk_split_dev — the
+// row count is read from device memory (clamped to [0, stride]: no row past the buffers is ever addressed) and db_t is [F][stride].
+// Everything after these two lines is the same code, so the same fp64 sums in the same order and the same merge.
+template <int KMAX, int QT, int RU, bool DEV>
 __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a) {
     __shared__ WaveTile<QT> tile_s[ON_WAVES];
     __shared__ double wl_v[ON_WAVES][QT][KMAX];          // the K best of every wave, ranked against each other after the barrier
     __shared__ int64_t wl_i[ON_WAVES][QT][KMAX];
     const int tid = threadIdx.x, lane = rat_lane(), wave = rat_wave();
     const int64_t ntiles = (a.Q + QT - 1) / QT;
-    const int64_t chunk = (a.N + a.splits - 1) / a.splits;
+    int64_t N = a.N, stride = a.N;
+    if constexpr (DEV) {
+        stride = a.stride;
+        N = *a.n_dev;
+        N = N < 0 ? 0 : (N > stride ? stride : N);
+    }
+    const int64_t chunk = (N + a.splits - 1) / a.splits;
     int parity = 0;
     for (int64_t item = blockIdx.x; item < ntiles * a.splits; item += gridDim.x) {
         const int64_t q0 = (item / a.splits) * QT;
         const int split = (int)(item % a.splits);
-        const int64_t lo = split * chunk < a.N ? split * chunk : a.N;        // ranges past the end of the pool are empty
-        const int64_t hi = lo + chunk < a.N ? lo + chunk : a.N;
+        const int64_t lo = split * chunk < N ? split * chunk : N;            // ranges past the end of the pool are empty
+        const int64_t hi = lo + chunk < N ? lo + chunk : N;
         double val[QT][KMAX], kth[QT];                     // kth = score of the current K-th entry (0 while the list is not full)
         int64_t idx[QT][KMAX];
 #pragma unroll
@@ -142,7 +153,7 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
 #pragma unroll
                 for (int u = 0; u < RU; ++u) {                                            // RU independent loads in flight per field
                     const int64_t n = n0 + (int64_t)u * ON_THREADS;
-                    id[u] = n < hi ? a.db_t[(int64_t)f * a.N + n] : -1;
+                    id[u] = n < hi ? a.db_t[(int64_t)f * stride + n] : -1;
                 }
 #pragma unroll
                 for (int t = 0; t < QT; ++t) {
@@ -301,6 +312,43 @@ int64_t auto_splits(int64_t n_qry, int64_t n_db, int topk) {
     return s < 1 ? 1 : s;
 }
 
+// both entry points of the split scan: the same two launches, the scan instantiated with the row count by value or from the device
+template <bool DEV>
+int launch_split(const char* who, const int32_t* db_t, const int32_t* qry_ids, const double* qry_idf, double* out_values,
+                 int64_t* out_indices, int64_t* out_lens, void* workspace, size_t workspace_bytes, int64_t n_db, const int64_t* n_dev,
+                 int64_t stride, int64_t n_qry, int n_fields, int topk, int splits, void* stream) {
+    const size_t need = (size_t)n_qry * (size_t)splits * (size_t)topk * (sizeof(double) + sizeof(int64_t));
+    if (workspace == nullptr || workspace_bytes < need)
+        return rat_fail(std::string(who) + ": workspace smaller than rat_bm25_topk_split_workspace()");
+    if (((uintptr_t)workspace & 7) != 0) return rat_fail(std::string(who) + ": workspace must be 8-byte aligned");
+    SplitArgs a{};
+    a.db_t = db_t;
+    a.qry = qry_ids;
+    a.idf = qry_idf;
+    a.part_val = static_cast<double*>(workspace);
+    a.part_idx = reinterpret_cast<int64_t*>(a.part_val + (size_t)n_qry * splits * topk);
+    a.out_val = out_values;
+    a.out_idx = out_indices;
+    a.out_len = out_lens;
+    a.N = n_db;
+    a.Q = n_qry;
+    a.F = n_fields;
+    a.K = topk;
+    a.splits = splits;
+    a.n_dev = n_dev;
+    a.stride = stride;
+    if (topk <= 8) {
+        const int64_t items = (n_qry + 3) / 4 * splits;
+        RAT_LAUNCH((bm25_scan_split_kernel<8, 4, 4, DEV>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
+    } else {
+        const int64_t items = n_qry * splits;
+        RAT_LAUNCH((bm25_scan_split_kernel<32, 1, 4, DEV>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
+    }
+    if (rat_check_launch(who) != 0) return -1;
+    RAT_LAUNCH(bm25_merge_kernel, (unsigned)(n_qry < 65536 ? n_qry : 65536), 64, 0, stream, a);
+    return rat_check_launch(who);
+}
+
 // ------------------------------------------------------------------------------------------------------------ query-side IDF mapping
 struct PrepArgs {
     const int32_t* ids;      // [Q][row_stride]
@@ -380,31 +428,84 @@ extern "C" int rat_bm25_topk_split(const int32_t* db_ids_field_major, const int3
             return rat_bm25_topk(db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, n_db, n_qry, n_fields, topk,
                                  stream);
     }
-    const size_t need = (size_t)n_qry * (size_t)splits * (size_t)topk * (sizeof(double) + sizeof(int64_t));
-    RAT_REQUIRE(workspace != nullptr && workspace_bytes >= need, "workspace smaller than rat_bm25_topk_split_workspace()");
-    RAT_REQUIRE(((uintptr_t)workspace & 7) == 0, "workspace must be 8-byte aligned");
-    SplitArgs a{};
-    a.db_t = db_ids_field_major;
-    a.qry = qry_ids;
-    a.idf = qry_idf;
-    a.part_val = static_cast<double*>(workspace);
-    a.part_idx = reinterpret_cast<int64_t*>(a.part_val + (size_t)n_qry * splits * topk);
-    a.out_val = out_values;
-    a.out_idx = out_indices;
-    a.out_len = out_lens;
-    a.N = n_db;
-    a.Q = n_qry;
-    a.F = n_fields;
-    a.K = topk;
-    a.splits = splits;
-    if (topk <= 8) {
-        const int64_t items = (n_qry + 3) / 4 * splits;
-        RAT_LAUNCH((bm25_scan_split_kernel<8, 4, 4>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
-    } else {
-        const int64_t items = n_qry * splits;
-        RAT_LAUNCH((bm25_scan_split_kernel<32, 1, 4>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
+    return launch_split<false>("rat_bm25_topk_split", db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
+                               workspace_bytes, n_db, nullptr, n_db, n_qry, n_fields, topk, splits, stream);
+}
+
+extern "C" int rat_bm25_topk_split_dev(const int32_t* db_ids_field_major, const int64_t* n_db_dev, const int32_t* qry_ids,
+                                       const double* qry_idf, double* out_values, int64_t* out_indices, int64_t* out_lens,
+                                       void* workspace, size_t workspace_bytes, int64_t capacity, int64_t n_qry, int n_fields, int topk,
+                                       int splits, void* stream) {
+    RAT_REQUIRE(db_ids_field_major && n_db_dev && qry_ids && qry_idf && out_values && out_indices && out_lens, "null pointer");
+    RAT_REQUIRE(capacity > 0 && n_qry > 0 && n_fields > 0 && topk > 0, "bad dims");
+    RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
+    RAT_REQUIRE(topk <= ON_KMAX, "topK > 32 is not supported");
+    RAT_REQUIRE(splits >= 0 && splits <= ON_MAX_SPLITS, "splits must be 0 (library's choice) or 1..4096");
+    // the launch shape may not depend on the row count (a captured launch serves the pool after it has grown): the rule of
+    // rat_bm25_topk_split applied to the CAPACITY; where it would hand over to the single-range kernel, one range through this one
+    if (splits == 0) splits = (int)auto_splits(n_qry, capacity, topk);
+    return launch_split<true>("rat_bm25_topk_split_dev", db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
+                              workspace_bytes, 0, n_db_dev, capacity, n_qry, n_fields, topk, splits, stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------ growing the pool
+namespace {
+
+struct AppendArgs {
+    const int32_t* ids;      // [M][L] the new rows
+    const float* labels;     // [M]
+    const int32_t* cols;     // [F]
+    int32_t* db_t;           // [F][capacity]
+    int32_t* pool_ids;       // [capacity][L]   (nullable, with pool_labels: an index without the scorer's row store)
+    float* pool_labels;      // [capacity]
+    int64_t* count;          // the header: rows in the pool
+    int64_t M, capacity;
+    int L, F;
+};
+
+// Work items e: [0, F * M) the field-major side — e = f * M + i, so 64 consecutive lanes write 64 consecutive rows of one column
+// (one 256-byte store per wave; the reads are L ints apart) — then [F * M, F * M + M * L) the row-major side, a straight copy
+// (pool_ids[n + i][c] is word n * L + e), the first M of which also carry a label.  n comes from the header; a batch that would not
+// fit writes nothing (the host refuses it before; this is the bound on the device).
+__global__ void __launch_bounds__(256) pool_append_kernel(AppendArgs a) {
+    const int64_t n = *a.count;
+    if (n < 0 || n + a.M > a.capacity) return;
+    const int64_t nt = (int64_t)a.F * a.M;
+    const int64_t total = nt + (a.pool_ids ? a.M * a.L : 0);
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        if (e < nt) {
+            const int64_t f = e / a.M, i = e % a.M;
+            a.db_t[f * a.capacity + n + i] = a.ids[i * a.L + a.cols[f]];
+        } else {
+            const int64_t r = e - nt;
+            a.pool_ids[n * a.L + r] = a.ids[r];
+            if (r < a.M) a.pool_labels[n + r] = a.labels[r];
+        }
     }
-    if (rat_check_launch("rat_bm25_topk_split") != 0) return -1;
-    RAT_LAUNCH(bm25_merge_kernel, (unsigned)(n_qry < 65536 ? n_qry : 65536), 64, 0, stream, a);
-    return rat_check_launch("rat_bm25_topk_split");
+}
+
+// the tail launch: the rows are in place (stream order), now they count
+__global__ void __launch_bounds__(64) pool_commit_kernel(int64_t* count, int64_t M, int64_t capacity) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        const int64_t n = *count;
+        if (n >= 0 && n + M <= capacity) *count = n + M;
+    }
+}
+
+}  // namespace
+
+extern "C" int rat_pool_append(const int32_t* ids, const float* labels, const int32_t* cols, int32_t* db_ids_field_major,
+                               int32_t* pool_ids, float* pool_labels, int64_t* n_db_dev, int64_t n_rows, int64_t capacity,
+                               int row_len, int n_fields, void* stream) {
+    RAT_REQUIRE(ids && cols && db_ids_field_major && n_db_dev, "null pointer");
+    RAT_REQUIRE((pool_ids == nullptr) == (pool_labels == nullptr), "pool_ids and pool_labels go together");
+    RAT_REQUIRE(pool_ids == nullptr || labels != nullptr, "null labels");
+    RAT_REQUIRE(n_rows > 0 && capacity > 0 && n_rows <= capacity && row_len > 0 && n_fields > 0, "bad dims");
+    RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
+    AppendArgs a{ids, labels, cols, db_ids_field_major, pool_ids, pool_labels, n_db_dev, n_rows, capacity, row_len, n_fields};
+    const int64_t blocks = (n_rows * (n_fields + (pool_ids ? row_len : 0)) + 255) / 256;
+    RAT_LAUNCH(pool_append_kernel, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
+    if (rat_check_launch("rat_pool_append") != 0) return -1;
+    RAT_LAUNCH(pool_commit_kernel, 1u, 64, 0, stream, n_db_dev, n_rows, capacity);
+    return rat_check_launch("rat_pool_append");
 }

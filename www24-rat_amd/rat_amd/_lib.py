@@ -155,6 +155,10 @@ _SIGNATURES = {
     "rat_bm25_query_prepare": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, _P]),
     "rat_bm25_topk_split_workspace": (c_size_t, [c_int64, c_int, c_int]),
     "rat_bm25_topk_split": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_size_t, c_int64, c_int64, c_int, c_int, c_int, _P]),
+    # a pool that grows in place: device-side append, and the scan / the assembly with the row count read from device memory
+    "rat_pool_append": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int, c_int, _P]),
+    "rat_bm25_topk_split_dev": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_size_t, c_int64, c_int64, c_int, c_int, c_int, _P]),
+    "rat_batch_assemble_dev": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

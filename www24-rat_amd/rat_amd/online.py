@@ -12,9 +12,17 @@ so ``OnlineScorer.score(ids)`` returns what the offline path returns for ``preco
 same rows.  From the third request of a batch size on the whole chain is ONE hipGraph on one stream (``graph.EvalGraph``'s scheme: a
 static input, weights read at replay time).
 
+The pool can grow.  ``RetrievalIndex(..., capacity=C)`` / ``OnlineScorer(..., capacity=C)`` allocate every device buffer for C rows
+once; ``append(rows)`` writes labelled rows behind the current ones on the device (``rat_pool_append``), and the scan and the assembly
+read the row count from device memory (``rat_bm25_topk_split_dev``, ``rat_batch_assemble_dev``) — so no address and no kernel argument
+of a request changes, and a request graph captured before an append serves the grown pool after it.  The IDF weights stay numpy's
+float64 ``log``: the index keeps the per-column (distinct ids, counts) on the host, merges the new rows into them and uploads the
+tables into the same device buffers.  After ``append`` the object answers exactly like a fresh one over ``concatenate([pool, rows])``.
+Without ``capacity`` nothing changes: the immutable index, the same kernels and launches as before.
+
 Not served online (refused at construction): exact-match columns (numbering the groups needs a host ``np.unique`` over pool and
-queries), label-wise retrieval, topK > 32, more than 32 retrieval columns, data-parallel models.  A changed pool is a new
-``RetrievalIndex``.
+queries), label-wise retrieval, topK > 32, more than 32 retrieval columns, data-parallel models.  The pool is append-only: rows are
+never evicted or deleted (a pool that shrinks is a new ``RetrievalIndex``).
 """
 import numpy as np
 import torch
@@ -39,12 +47,31 @@ def _as_device_ids(ids, device):
     return ids.contiguous()
 
 
+def _host_rows(rows, row_len):
+    """rows [M, L + 1] (numpy / host or device tensor; label last) -> (ids int32 [M, L], ids as int [M, L], labels fp32 [M]) on the host,
+    converted the way the constructors convert the pool"""
+    if torch.is_tensor(rows):
+        rows = rows.detach().cpu().numpy()
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or len(rows) == 0:
+        raise ValueError("rows must be a non-empty [M, L + 1] encoded table (label last), got shape %s" % (tuple(rows.shape),))
+    if rows.shape[1] != row_len + 1:
+        raise ValueError("rows have %d columns, the pool's rows have %d (%d ids and the label)" % (rows.shape[1], row_len + 1, row_len))
+    as_int = rows[:, :-1].astype(int)
+    return np.ascontiguousarray(retrieval._as_int32(as_int, "appended")), as_int, np.ascontiguousarray(rows[:, -1].astype(np.float32))
+
+
 class RetrievalIndex:
     """A retrieval pool resident in HBM: its id columns field-major (what the top-K scan streams) and its per-column IDF tables
     (built once, on the host, by ``retrieval.idf_tables`` — numpy's float64 ``log``, so the weights are bit-identical to the offline
-    path's).  ``retrieve(ids)`` is ``BM25_topk_retrieval_v4(pool, ids[:, cols], topK=K)`` of one query batch, device tensors out."""
+    path's).  ``retrieve(ids)`` is ``BM25_topk_retrieval_v4(pool, ids[:, cols], topK=K)`` of one query batch, device tensors out.
 
-    def __init__(self, pool_array, col_indices, topK, device, lib=None, exact_match_col_indices=None, splits=0):
+    ``capacity`` (>= len(pool)): the buffers are allocated for that many rows, once, and ``append(rows)`` adds rows in place; the
+    index then equals a fresh one over the concatenated pool.  Append-only (no eviction, no deletion).  Memory: ``db_t`` is
+    4 F capacity bytes; column f's IDF table is reserved for (its distinct ids now + capacity - len(pool)) entries of 12 bytes — every
+    appended row adds at most one distinct id per column."""
+
+    def __init__(self, pool_array, col_indices, topK, device, lib=None, exact_match_col_indices=None, splits=0, capacity=None):
         if exact_match_col_indices:
             raise ValueError("online retrieval does not support exact-match columns (exact_match_col_indices=%s): numbering the groups "
                              "needs a host pass over pool and queries" % (list(exact_match_col_indices),))
@@ -63,11 +90,16 @@ class RetrievalIndex:
         self._lib = lib or get_lib()
         self.device = dev = torch.device(device)
         db = pool_array[:, cols].astype(int)                                   # as precompute_retrieval slices the pool
-        tables = retrieval.idf_tables(db)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)        # noqa: E731
         self.n_db = len(db)
-        self.db_t = up(retrieval._as_int32(db, "pool").T)                      # [F][N] field-major
+        self.capacity = None
+        self._col_list = cols
         self.cols = up(np.asarray(cols, dtype=np.int32))
+        if capacity is not None:
+            self._init_growable(db, int(capacity))
+            return
+        tables = retrieval.idf_tables(db)
+        self.db_t = up(retrieval._as_int32(db, "pool").T)                      # [F][N] field-major
         self.table_ids = up(np.concatenate([retrieval._as_int32(v, "pool") for v, _ in tables]))
         self.table_idf = up(np.concatenate([w for _, w in tables]).astype(np.float64))
         self.table_offsets = up(np.concatenate([[0], np.cumsum([len(v) for v, _ in tables])]).astype(np.int64))
@@ -80,7 +112,64 @@ class RetrievalIndex:
         if ids.shape[0] == 0:
             raise ValueError("empty request")
         qry_ids, qry_idf = ops.bm25_query_prepare(ids, self.cols, self.table_ids, self.table_idf, self.table_offsets, lib=self._lib)
+        if self.capacity is not None:
+            return ops.bm25_topk_split_dev(self.db_t, self.count, qry_ids, qry_idf, self.topK, splits=self.splits, lib=self._lib)
         return ops.bm25_topk_split(self.db_t, qry_ids, qry_idf, self.topK, splits=self.splits, lib=self._lib)
+
+    def __len__(self):
+        return self.n_db
+
+    # ---- the growable form -------------------------------------------------------------------------------------------
+    def _init_growable(self, db, capacity):
+        if capacity < len(db):
+            raise ValueError("capacity = %d is smaller than the pool (%d rows)" % (capacity, len(db)))
+        dev, n, F = self.device, len(db), db.shape[1]
+        self.capacity = capacity
+        self.db_t = torch.zeros((F, capacity), dtype=torch.int32, device=dev)
+        self.db_t[:, :n] = torch.from_numpy(np.ascontiguousarray(retrieval._as_int32(db, "pool").T)).to(dev)
+        self.count = torch.full((1,), n, dtype=torch.int64, device=dev)        # the header the kernels read the row count from
+        # host mirror of the tables' integer half: per column (sorted distinct ids, counts); the weights are derived from it
+        self._counts = [np.unique(db[:, c], return_counts=True) for c in range(F)]
+        table_cap = sum(len(v) for v, _ in self._counts) + F * (capacity - n)
+        self.table_ids = torch.zeros(table_cap, dtype=torch.int32, device=dev)
+        self.table_idf = torch.zeros(table_cap, dtype=torch.float64, device=dev)
+        self.table_offsets = torch.zeros(F + 1, dtype=torch.int64, device=dev)
+        self._upload_tables()
+
+    def _upload_tables(self):
+        """retrieval.idf_tables' arithmetic (numpy's float64 log of n / counts) over the mirrored counts -> the SAME device buffers,
+        packed front to back (rat_bm25_query_prepare reads the extents from table_offsets on the device)"""
+        ids = np.concatenate([retrieval._as_int32(v, "pool") for v, _ in self._counts])
+        idf = np.concatenate([np.log(self.n_db / c) for _, c in self._counts]).astype(np.float64)
+        off = np.concatenate([[0], np.cumsum([len(v) for v, _ in self._counts])]).astype(np.int64)
+        assert len(ids) <= self.table_ids.numel()
+        self.table_ids[:len(ids)].copy_(torch.from_numpy(ids))
+        self.table_idf[:len(idf)].copy_(torch.from_numpy(idf))
+        self.table_offsets.copy_(torch.from_numpy(off))
+
+    def append(self, rows, _pool_ids=None, _pool_labels=None):
+        """rows [M, L + 1] (label last; numpy, host or device tensor) become pool rows n .. n + M - 1: retrievable by the next request,
+        and every IDF weight moves (N and the counts).  Ordered with the requests on the current stream.  ValueError — and nothing
+        written — for an index without ``capacity``, rows that do not fit, a wrong column count or an id outside int32."""
+        if self.capacity is None:
+            raise ValueError("this index was built without capacity: its pool is immutable (pass capacity= to append rows)")
+        ids32, as_int, labels = _host_rows(rows, self.row_len)
+        M = len(ids32)
+        if self.n_db + M > self.capacity:
+            raise ValueError("appending %d rows to %d exceeds the capacity of %d rows" % (M, self.n_db, self.capacity))
+        for f, c in enumerate(self._col_list):                                 # np.unique over the M new rows only
+            vals, counts = self._counts[f]
+            u, uc = np.unique(as_int[:, c], return_counts=True)
+            pos = np.searchsorted(vals, u)
+            hit = vals[np.minimum(pos, len(vals) - 1)] == u
+            counts = counts.copy()
+            counts[pos[hit]] += uc[hit]
+            self._counts[f] = (np.insert(vals, pos[~hit], u[~hit]), np.insert(counts, pos[~hit], uc[~hit]))
+        self.n_db += M
+        dev = self.device
+        ops.pool_append(torch.from_numpy(ids32).to(dev), torch.from_numpy(labels).to(dev), self.cols, self.db_t, self.count,
+                        _pool_ids, _pool_labels, lib=self._lib)
+        self._upload_tables()
 
 
 class _RequestGraph:
@@ -105,13 +194,15 @@ class OnlineScorer:
     """``score(ids)``: fp32 [B] predictions of a trained model for fresh encoded rows ``ids`` [B, L], the neighbours retrieved from
     ``pool_array`` ([N, L + 1], label last) on the spot.  ``retrieval_configs`` is the dataset's block (``topK``, ``used_cols`` or
     ``used_col_indices``, ...).  ``graph=True``: after ``graph_warmup`` eager requests of a batch size (<= ``graph_max_batch``) the
-    chain is captured and replayed; the weights are read at replay time, so the graph survives optimizer steps and load_state_dict."""
+    chain is captured and replayed; the weights are read at replay time, so the graph survives optimizer steps and load_state_dict.
+    ``capacity``: room for that many pool rows; ``append(rows)`` then adds labelled rows in place and the captured graphs stay valid
+    (they read the row count from device memory).  Append-only."""
 
     graph_warmup = 2
     graph_max_batch = 4096
     graph_sizes = 16               # at most this many request sizes get a graph; others stay eager
 
-    def __init__(self, model, pool_array, retrieval_configs, graph=True, lib=None):
+    def __init__(self, model, pool_array, retrieval_configs, graph=True, lib=None, capacity=None):
         cfg = retrieval_configs
         if cfg.get("exact_match_col_indices") or cfg.get("exact_match_cols"):
             raise ValueError("online scoring does not support exact-match columns (exact_match_cols / exact_match_col_indices are set)")
@@ -125,10 +216,17 @@ class OnlineScorer:
         self.model = model
         self.device = model.device
         self._lib = lib or model._lib
-        self.index = RetrievalIndex(pool_array, cols, cfg["topK"], self.device, lib=self._lib)
+        self.index = RetrievalIndex(pool_array, cols, cfg["topK"], self.device, lib=self._lib, capacity=capacity)
         pool_array = np.asarray(pool_array)
         self.pool_ids = torch.from_numpy(np.ascontiguousarray(pool_array[:, :-1].astype(np.int32))).to(self.device)
         self.pool_labels = torch.from_numpy(np.ascontiguousarray(pool_array[:, -1].astype(np.float32))).to(self.device)
+        if self.index.capacity is not None:                                    # the row store at full size, the pool in front
+            n, cap = len(pool_array), self.index.capacity
+            ids, labels = self.pool_ids, self.pool_labels
+            self.pool_ids = torch.zeros((cap, ids.shape[1]), dtype=torch.int32, device=self.device)
+            self.pool_labels = torch.zeros(cap, dtype=torch.float32, device=self.device)
+            self.pool_ids[:n] = ids
+            self.pool_labels[:n] = labels
         self.graph = bool(graph)
         self._consts = {}              # request size -> (rows = arange(B), labels = zeros(B))
         self._graphs = {}              # key -> [eager requests seen, _RequestGraph | False | None]
@@ -145,11 +243,18 @@ class OnlineScorer:
         rows, labels = self._constants(ids.shape[0])
         _values, indices, _lens = self.index.retrieve(ids)
         # the request is the query table, the kernel's own index output the neighbour lists; -1 keeps its numpy meaning, as offline
+        if self.index.capacity is not None:                                    # ... counted back from the pool's last LIVE row
+            return ops.batch_assemble_dev(ids, labels, self.pool_ids, self.pool_labels, indices, rows, self.index.count, lib=self._lib)
         return ops.batch_assemble(ids, labels, self.pool_ids, self.pool_labels, indices, rows, lib=self._lib)
 
     def _score_eager(self, ids):
         y_pred, _loss, _reg, _saved = self.model._run_forward(self._assemble(ids), save=False, with_reg=False)
         return y_pred.reshape(-1)
+
+    def append(self, rows):
+        """``RetrievalIndex.append`` plus the row store (ids and labels of the new rows, the same launch).  Afterwards the scorer equals
+        ``OnlineScorer(model, np.concatenate([pool, rows]), cfg)``; captured request graphs are kept and serve the grown pool."""
+        self.index.append(rows, self.pool_ids, self.pool_labels)
 
     def batch(self, ids):
         """-> data.DeviceBatch (idx [B, 1 + K, L], label_ids [B, 1 + K], y_true = zeros): what the model's forward consumes"""

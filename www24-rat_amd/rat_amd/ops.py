@@ -961,3 +961,55 @@ def bm25_topk_split(db_t, qry_ids, qry_idf, topk, splits=0, lib=None):
     lib.call("rat_bm25_topk_split", _p(db_t), _p(qry_ids), _p(qry_idf), _p(out_v), _p(out_i), _p(out_l), _p(ws), ws.numel() * 8, N, Q, F,
              int(topk), int(splits), _stream(db_t))
     return out_v, out_i, out_l
+
+
+# ----------------------------------------------------------------------------- K6c: a pool that grows in place (rat_amd/online.py)
+def pool_append(ids, labels, cols, db_t, count, pool_ids=None, pool_labels=None, lib=None):
+    """rows `ids` int32 [M, L] / `labels` fp32 [M] (device) -> rows n .. n + M - 1 of db_t int32 [F, capacity] (transposed, the columns
+    `cols`), pool_ids int32 [capacity, L] and pool_labels fp32 [capacity]; n = count[0] (int64, device) becomes n + M, on the device"""
+    lib = lib or get_lib()
+    _chk(ids, torch.int32, "ids"), _chk(labels, name="labels"), _chk(cols, torch.int32, "cols"), _chk(db_t, torch.int32, "db_t")
+    _chk(count, torch.int64, "count"), _chk(pool_ids, torch.int32, "pool_ids"), _chk(pool_labels, name="pool_labels")
+    M, L = ids.shape
+    F, capacity = db_t.shape
+    assert cols.numel() == F and labels.numel() == M and count.numel() >= 1 and (pool_ids is None) == (pool_labels is None)
+    if pool_ids is not None:
+        assert tuple(pool_ids.shape) == (capacity, L) and pool_labels.numel() == capacity
+    lib.call("rat_pool_append", _p(ids), _p(labels), _p(cols), _p(db_t), _p(pool_ids), _p(pool_labels), _p(count), M, capacity, L, F,
+             _stream(db_t))
+
+
+def bm25_topk_split_dev(db_t, count, qry_ids, qry_idf, topk, splits=0, lib=None):
+    """bm25_topk_split over the first count[0] (int64, device) rows of db_t int32 [F, capacity]; splits = 0: chosen from the capacity"""
+    lib = lib or get_lib()
+    _chk(db_t, torch.int32, "db_t"), _chk(qry_ids, torch.int32, "qry_ids"), _chk(qry_idf, torch.float64, "qry_idf")
+    _chk(count, torch.int64, "count")
+    F, capacity = db_t.shape
+    Q = qry_ids.shape[0]
+    assert tuple(qry_ids.shape) == (Q, F) and tuple(qry_idf.shape) == (Q, F) and count.numel() >= 1
+    dev = db_t.device
+    nbytes = lib.size("rat_bm25_topk_split_workspace", Q, int(topk), int(splits))
+    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    out_v = torch.empty((Q, topk), dtype=torch.float64, device=dev)
+    out_i = torch.empty((Q, topk), dtype=torch.int64, device=dev)
+    out_l = torch.empty((Q,), dtype=torch.int64, device=dev)
+    lib.call("rat_bm25_topk_split_dev", _p(db_t), _p(count), _p(qry_ids), _p(qry_idf), _p(out_v), _p(out_i), _p(out_l), _p(ws),
+             ws.numel() * 8, capacity, Q, F, int(topk), int(splits), _stream(db_t))
+    return out_v, out_i, out_l
+
+
+def batch_assemble_dev(data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, count, lib=None):
+    """batch_assemble against a pool whose row count is count[0] (int64, device): a negative neighbour counts back from there"""
+    lib = lib or get_lib()
+    _chk(data_ids, torch.int32, "data_ids"), _chk(pool_ids, torch.int32, "pool_ids")
+    _chk(data_labels, name="data_labels"), _chk(pool_labels, name="pool_labels")
+    _chk(retr_indices, torch.int64, "retr_indices"), _chk(rows, torch.int64, "rows"), _chk(count, torch.int64, "count")
+    Q, L = data_ids.shape
+    K, B = retr_indices.shape[1], rows.numel()
+    dev = data_ids.device
+    idx = torch.empty((B, K + 1, L), dtype=torch.int32, device=dev)
+    label_ids = torch.empty((B, K + 1), dtype=torch.int32, device=dev)
+    y_true = torch.empty((B,), dtype=torch.float32, device=dev)
+    lib.call("rat_batch_assemble_dev", _p(data_ids), _p(data_labels), _p(pool_ids), _p(pool_labels), _p(retr_indices), _p(rows),
+             _p(idx), _p(label_ids), _p(y_true), Q, _p(count), B, K, L, _stream(data_ids))
+    return idx, label_ids, y_true
