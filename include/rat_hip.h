@@ -364,7 +364,8 @@ int rat_bm25_topk_split(const int32_t* db_ids_field_major, const int32_t* qry_id
  * pool_ids[n + i][:], pool_labels[n + i] and, transposed, db_ids_field_major[f][n + i] = ids[i][cols[f]] (64 consecutive rows of a
  * column per wave); a one-thread tail launch then sets *n_db_dev = n + n_rows.  Both read n on the device: appends queue back to back
  * without a synchronisation.  n + n_rows > capacity writes nothing and leaves the count (the caller checks beforehand).  pool_ids and
- * pool_labels may both be NULL (an index without the row store; labels is then ignored).  Append-only: rows are never removed. */
+ * pool_labels may both be NULL (an index without the row store; labels is then ignored).  This form never removes a row; the ring
+ * form below does. */
 int rat_pool_append(const int32_t* ids, const float* labels, const int32_t* cols, int32_t* db_ids_field_major, int32_t* pool_ids,
                     float* pool_labels, int64_t* n_db_dev, int64_t n_rows, int64_t capacity, int row_len, int n_fields, void* stream);
 /* rat_bm25_topk_split over the first *n_db_dev rows of a [n_fields][capacity] pool.  splits = 0: rat_bm25_topk_split's rule applied
@@ -380,6 +381,31 @@ int rat_bm25_topk_split_dev(const int32_t* db_ids_field_major, const int64_t* n_
 int rat_batch_assemble_dev(const int32_t* data_ids, const float* data_labels, const int32_t* pool_ids, const float* pool_labels,
                            const int64_t* retr_indices, const int64_t* rows, int32_t* idx, int32_t* label_ids, float* y_true,
                            int64_t Q, const int64_t* n_pool_dev, int B, int K, int L, void* stream);
+
+/* A pool that slides (additive in ABI v9 as well): the same three buffers used as a RING.  The header header_dev is two int64 in device
+ * memory, {n, head}: n live rows, head = the physical slot of the oldest.  LOGICAL row i (0 = oldest, n - 1 = newest) lives in slot
+ * head + i, minus capacity when that is >= capacity.  Everything a caller sees is logical: the indices the scan returns, the tie rule
+ * (score descending, logical index ascending — the older row wins) and the neighbour indices the assembly takes.
+ *
+ * rat_pool_push: rat_pool_append's work with E = max(0, n + n_rows - capacity): row i of the batch goes to slot head + n + i (wrapped)
+ * of all three stores, then a one-thread tail launch sets head = head + E (wrapped), n = n + n_rows - E — the E oldest rows leave.
+ * Both launches read the header on the device (pushes queue back to back).  n_rows > capacity writes nothing and leaves the header.
+ * rat_pool_evict: a one-thread launch, head = head + n_rows (wrapped), n = n - n_rows; nothing happens for n_rows < 0 or n_rows >= n
+ * (the pool never becomes empty).
+ * rat_bm25_topk_split_ring: rat_bm25_topk_split_dev over the n live rows in logical order (n clamped to [0, capacity], head to
+ * [0, capacity)); ranges are cut over the logical rows, only the address of the id load is physical.  The result equals rat_bm25_topk
+ * over a contiguous copy of the live rows, oldest first, bit for bit, for every head.
+ * rat_batch_assemble_ring: rat_batch_assemble_dev with logical neighbour indices — a negative one counts back from n first, then the
+ * index is mapped to its slot. */
+int rat_pool_push(const int32_t* ids, const float* labels, const int32_t* cols, int32_t* db_ids_field_major, int32_t* pool_ids,
+                  float* pool_labels, int64_t* header_dev, int64_t n_rows, int64_t capacity, int row_len, int n_fields, void* stream);
+int rat_pool_evict(int64_t* header_dev, int64_t n_rows, int64_t capacity, void* stream);
+int rat_bm25_topk_split_ring(const int32_t* db_ids_field_major, const int64_t* header_dev, const int32_t* qry_ids, const double* qry_idf,
+                             double* out_values, int64_t* out_indices, int64_t* out_lens, void* workspace, size_t workspace_bytes,
+                             int64_t capacity, int64_t n_qry, int n_fields, int topk, int splits, void* stream);
+int rat_batch_assemble_ring(const int32_t* data_ids, const float* data_labels, const int32_t* pool_ids, const float* pool_labels,
+                            const int64_t* retr_indices, const int64_t* rows, int32_t* idx, int32_t* label_ids, float* y_true,
+                            int64_t Q, const int64_t* header_dev, int64_t capacity, int B, int K, int L, void* stream);
 
 /* ---- K3: prediction head -----------------------------------------------------------------------------
  * Plain fp32 GEMM on MFMA for MLP_Layer's nn.Linear (deep.py:126-141) forward / dgrad / wgrad:

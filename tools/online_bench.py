@@ -15,6 +15,10 @@ RetrievalIndex.append(M rows) on an index with reserved capacity against the onl
 over np.concatenate([pool, rows]) — for M in {1, 64, 4096}; (ii) replayed score() latency of a scorer with capacity (1.4 M rows in
 room for 2 M) against the immutable scorer over the same pool at B in {1, 16, 256}.  Host clock around a synchronise, the two sides
 alternating round by round in one process, at least 0.5 s of timed work per point and side; mean, and min .. max over the rounds.
+--window — the sliding pool instead (profiles/online/window_bench.txt), same geometry, clock and alternation: (i) replayed score() of a
+scorer with capacity and window=True against the capacity-mode scorer over the same rows, at B in {1, 16, 256}, once with the ring's
+head at 0 and once after enough pushes that the live rows wrap through the end of the buffer; (ii) append(M) on a FULL window (the M
+oldest rows leave) against a new RetrievalIndex over the shifted pool, for M in {1, 64, 4096}.
 There is no CPU fallback: without a GPU the tool exits with an error."""
 import argparse
 import os
@@ -246,11 +250,100 @@ def part_append(emit, quick):
         emit("B %4d | capacity %s | immutable %s | capacity / immutable = %.4f" % (B, _stats(per["capacity"]), _stats(per["immutable"]), a / b))
 
 
+def _replay_rounds(sides, ids, min_s, rounds_of=200):
+    """sides: {label: scorer with the request captured} -> {label: [us per request of every round]}, the sides alternating"""
+    per = {k: [] for k in sides}
+    while min(sum(v) for v in per.values()) * rounds_of / 1e6 < min_s:
+        for label, sc in sides.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(rounds_of):
+                sc.score(ids)
+                torch.cuda.synchronize()
+            per[label].append((time.perf_counter() - t0) / rounds_of * 1e6)
+    return per
+
+
+def part_window(emit, quick):
+    from rat_amd.online import OnlineScorer, RetrievalIndex
+    name, model, rows, vocab, cfg, n_pool, capacity = _movielens(quick)
+    dev, K, cols = torch.device("cuda:0"), cfg["topK"], cfg["used_col_indices"]
+    min_s = 0.05 if quick else MIN_TIMED_MS / 1e3
+    pool = rows(n_pool)
+    rs = np.random.RandomState(5)
+    requests = {B: torch.from_numpy(np.stack([rs.randint(0, v, size=B) for v in vocab], axis=1).astype(np.int32)).to(dev)
+                for B in (1, 16, 256)}
+    emit("== window (i): replayed OnlineScorer.score() [us per request], %s, %d live rows in a capacity of %d: window=True against the "
+         "capacity-mode scorer over the same rows; host clock + synchronise, rounds of 200 requests alternating" % (name, n_pool, capacity))
+    ring = OnlineScorer(model, pool, cfg, graph=True, capacity=capacity, window=True)
+    push = capacity - n_pool + n_pool // 2                                 # afterwards half of the live rows lie before the wrap
+    for state in ("head = 0", "wrapped"):
+        if state == "wrapped":
+            cur = pool
+            while push > 0:                                                # the window fills, then slides: n stays at the capacity
+                new = rows(min(push, 200_000))
+                ring.append(new)
+                cur = np.concatenate([cur, new])[-capacity:]
+                push -= len(new)
+            ring.evict(capacity - n_pool)                                  # ... and back to n_pool live rows, as before
+            cur = cur[capacity - n_pool:]
+            n, head = ring.index.count.cpu().tolist()
+            assert n == n_pool and head + n > capacity, (n, head)
+            emit("   after the pushes: n = %d, head = %d — %d live rows before the wrap, %d after it" % (n, head, capacity - head,
+                                                                                                      n - (capacity - head)))
+        else:
+            cur = pool
+        flat = OnlineScorer(model, cur, cfg, graph=True, capacity=capacity)
+        for B, ids in requests.items():
+            for sc in (ring, flat):
+                for _ in range(5):
+                    sc.score(ids)
+                torch.cuda.synchronize()
+                assert any(e[1] for e in sc._graphs.values()), "the request was not captured"
+            assert torch.equal(ring.score(ids), flat.score(ids)), "window scorer != capacity scorer over the same rows"
+            per = _replay_rounds({"window": ring, "capacity": flat}, ids, min_s)
+            a, b = (sum(per[k]) / len(per[k]) for k in ("window", "capacity"))
+            emit("%-8s B %4d | window %s | capacity %s | window / capacity = %.4f" % (state, B, _stats(per["window"]),
+                                                                                     _stats(per["capacity"]), a / b))
+        del flat
+    del ring
+
+    emit("== window (ii): taking M labelled rows into a FULL window of %d rows (%d columns) [ms per call]: RetrievalIndex.append (the M "
+         "oldest rows leave) against a new RetrievalIndex over np.concatenate([pool[M:], rows]) (concatenate included); host clock + "
+         "synchronise, alternating" % (n_pool, len(cols)))
+    index = RetrievalIndex(pool, cols, K, dev, capacity=n_pool, window=True)
+    cur = pool
+    for M in (1, 64, 4096):
+        t_app, t_new = [], []
+        while sum(t_app) < min_s or sum(t_new) < min_s or len(t_app) < 3 or len(t_new) < 3:
+            new = rows(M)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            index.append(new)
+            torch.cuda.synchronize()
+            t_app.append((time.perf_counter() - t0) * 1e3)
+            if sum(t_new) < min_s or len(t_new) < 3:     # the same rows into the same pool, the immutable way
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fresh = RetrievalIndex(np.concatenate([cur[M:], new]), cols, K, dev)
+                torch.cuda.synchronize()
+                t_new.append((time.perf_counter() - t0) * 1e3)
+                del fresh
+            cur = np.concatenate([cur[M:], new])
+        a, b = sum(t_app) / len(t_app), sum(t_new) / len(t_new)
+        emit("M %5d | append %s | new index %s | append / new index = %.5f (%.0fx)" % (M, _stats(t_app), _stats(t_new), a / b, b / a))
+    fresh = RetrievalIndex(cur, cols, K, dev)
+    for g, w in zip(index.retrieve(requests[16]), fresh.retrieve(requests[16])):
+        assert torch.equal(g.view(torch.int64), w.view(torch.int64)), "window index != fresh index"
+    emit("   (afterwards retrieve() equals a fresh index over the live rows, bit for bit; head = %d)" % index.count.cpu().tolist()[1])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the report to this file")
     ap.add_argument("--quick", action="store_true", help="a few small points only (plumbing check)")
     ap.add_argument("--append", action="store_true", help="measure the growing pool (append against a new index; replay with capacity)")
+    ap.add_argument("--window", action="store_true", help="measure the sliding pool (replay with window=True; append on a full window)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("online_bench.py measures on the GPU; no GPU is visible and there is no CPU fallback")
@@ -266,6 +359,9 @@ def main():
     emit("tools/online_bench.py on %s, torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
     if args.append:
         part_append(emit, args.quick)
+        return
+    if args.window:
+        part_window(emit, args.quick)
         return
     part1(emit, args.quick)
     part2(emit, args.quick)

@@ -28,17 +28,30 @@ struct BatchArgs {
     float* y_true;
     int64_t Q, N;
     int B, K, L;
-    const int64_t* n_dev;    // DEV only: the pool's row count in device memory (N is then not used)
+    const int64_t* n_dev;    // POOL_DEV / POOL_RING: the pool's row count in device memory (N is then not used); POOL_RING: two
+                             // words, {row count, physical slot of the oldest live row}
+    int64_t capacity;        // POOL_RING only: slots of the ring
 };
+
+enum { POOL_HOST = 0, POOL_DEV = 1, POOL_RING = 2 };
 
 // one thread per output id: consecutive threads write consecutive ints of idx (coalesced); the source rows are L ints
 // (80 bytes at the north-star config) fetched by L neighbouring lanes
 // DEV: the pool's row count — what a negative neighbour index counts back from — is read from device memory: the pool of an online
 // index with reserved capacity grows under a captured request, and -1 must keep resolving to its last LIVE row
-template <bool DEV>
+// POOL_RING: the pool is a ring (a sliding window): a neighbour index is a LOGICAL position (0 = oldest live row; a negative one counts
+// back from the row count first) and lives in slot head + index, minus capacity when that is >= capacity.  Count, head and the
+// logical index are clamped to their domains, so no slot outside the buffers is addressed whatever the header holds.
+template <int POOL>
 __global__ void __launch_bounds__(256) batch_assemble_kernel(BatchArgs a) {
     const int T = a.K + 1;
-    const int64_t N = DEV ? *a.n_dev : a.N;
+    int64_t N = POOL != POOL_HOST ? a.n_dev[0] : a.N;
+    [[maybe_unused]] int64_t head = 0;
+    if constexpr (POOL == POOL_RING) {
+        N = N < 1 ? 1 : (N > a.capacity ? a.capacity : N);
+        head = a.n_dev[1];
+        head = head < 0 ? 0 : (head >= a.capacity ? a.capacity - 1 : head);
+    }
     const int64_t total = (int64_t)a.B * T * a.L;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
         const int c = (int)(e % a.L);
@@ -56,6 +69,11 @@ __global__ void __launch_bounds__(256) batch_assemble_kernel(BatchArgs a) {
         } else {
             int64_t nb = a.retr_indices[row * a.K + (t - 1)];
             if (nb < 0) nb += N;
+            if constexpr (POOL == POOL_RING) {
+                nb = nb < 0 ? 0 : (nb >= N ? N - 1 : nb);
+                nb += head;
+                nb = nb >= a.capacity ? nb - a.capacity : nb;
+            }
             v = a.pool_ids[nb * a.L + c];
             if (c == 0) a.label_ids[bt] = (int32_t)a.pool_labels[nb];
         }
@@ -71,10 +89,10 @@ extern "C" int rat_batch_assemble(const int32_t* data_ids, const float* data_lab
     RAT_REQUIRE(data_ids && data_labels && pool_ids && pool_labels && rows && idx && label_ids && y_true, "null pointer");
     RAT_REQUIRE(K == 0 || retr_indices != nullptr, "null retr_indices");
     RAT_REQUIRE(B > 0 && K >= 0 && L > 0 && Q > 0 && N > 0, "bad dims");
-    BatchArgs a{data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, idx, label_ids, y_true, Q, N, B, K, L, nullptr};
+    BatchArgs a{data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, idx, label_ids, y_true, Q, N, B, K, L, nullptr, 0};
     const int64_t total = (int64_t)B * (K + 1) * L;
     const int64_t blocks = (total + 255) / 256;
-    RAT_LAUNCH(batch_assemble_kernel<false>, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
+    RAT_LAUNCH(batch_assemble_kernel<POOL_HOST>, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
     return rat_check_launch("rat_batch_assemble");
 }
 
@@ -85,11 +103,25 @@ extern "C" int rat_batch_assemble_dev(const int32_t* data_ids, const float* data
     RAT_REQUIRE(data_ids && data_labels && pool_ids && pool_labels && rows && idx && label_ids && y_true && n_pool_dev, "null pointer");
     RAT_REQUIRE(K == 0 || retr_indices != nullptr, "null retr_indices");
     RAT_REQUIRE(B > 0 && K >= 0 && L > 0 && Q > 0, "bad dims");
-    BatchArgs a{data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, idx, label_ids, y_true, Q, 0, B, K, L, n_pool_dev};
+    BatchArgs a{data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, idx, label_ids, y_true, Q, 0, B, K, L, n_pool_dev, 0};
     const int64_t total = (int64_t)B * (K + 1) * L;
     const int64_t blocks = (total + 255) / 256;
-    RAT_LAUNCH(batch_assemble_kernel<true>, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
+    RAT_LAUNCH(batch_assemble_kernel<POOL_DEV>, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
     return rat_check_launch("rat_batch_assemble_dev");
+}
+
+extern "C" int rat_batch_assemble_ring(const int32_t* data_ids, const float* data_labels, const int32_t* pool_ids,
+                                       const float* pool_labels, const int64_t* retr_indices, const int64_t* rows, int32_t* idx,
+                                       int32_t* label_ids, float* y_true, int64_t Q, const int64_t* header_dev, int64_t capacity, int B,
+                                       int K, int L, void* stream) {
+    RAT_REQUIRE(data_ids && data_labels && pool_ids && pool_labels && rows && idx && label_ids && y_true && header_dev, "null pointer");
+    RAT_REQUIRE(K == 0 || retr_indices != nullptr, "null retr_indices");
+    RAT_REQUIRE(B > 0 && K >= 0 && L > 0 && Q > 0 && capacity > 0, "bad dims");
+    BatchArgs a{data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, idx, label_ids, y_true, Q, 0, B, K, L, header_dev, capacity};
+    const int64_t total = (int64_t)B * (K + 1) * L;
+    const int64_t blocks = (total + 255) / 256;
+    RAT_LAUNCH(batch_assemble_kernel<POOL_RING>, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
+    return rat_check_launch("rat_batch_assemble_ring");
 }
 
 // ---- inputs_to_device + the label-token rule for a batch that is ALREADY on the device (ABI v8) --------------------------------------

@@ -100,16 +100,23 @@ struct SplitArgs {
     double* out_val;         // [Q][K]
     int64_t* out_idx;        // [Q][K]
     int64_t* out_len;        // [Q]
-    int64_t N, Q;            // N: rows of the pool — DEV: read from *n_dev instead, and N is not used
+    int64_t N, Q;            // N: rows of the pool — POOL_DEV / POOL_RING: read from *n_dev instead, and N is not used
     int F, K, splits;
-    const int64_t* n_dev;    // DEV only: the pool's current row count (the header a RetrievalIndex with capacity keeps)
-    int64_t stride;          // DEV only: column stride of db_t (the capacity); otherwise the stride is N
+    const int64_t* n_dev;    // POOL_DEV: the pool's current row count (the header a RetrievalIndex with capacity keeps);
+                             // POOL_RING: that header is two words, {row count, physical slot of the oldest live row}
+    int64_t stride;          // POOL_DEV / POOL_RING: column stride of db_t (the capacity); otherwise the stride is N
 };
 
-// DEV = false: rat_bm25_topk_split (row count and column stride are the host argument N).  DEV = true: rat_bm25_topk_split_dev — the
+// Where the scan takes the pool's extent from.
+// POOL_HOST: rat_bm25_topk_split (row count and column stride are the host argument N).  POOL_DEV: rat_bm25_topk_split_dev — the
 // row count is read from device memory (clamped to [0, stride]: no row past the buffers is ever addressed) and db_t is [F][stride].
-// Everything after these two lines is the same code, so the same fp64 sums in the same order and the same merge.
-template <int KMAX, int QT, int RU, bool DEV>
+// POOL_RING: rat_bm25_topk_split_ring — db_t is a ring of `stride` slots: the header also holds `head` (clamped to [0, stride)), and
+// LOGICAL row n (0 = oldest) lives in slot head + n, minus stride when that is >= stride (head + n < 2 stride, so a compare and a
+// subtract).  Only the address of the one id load is physical: ranges, list entries, ties and the merge all see logical rows.
+// Everything after the prologue is the same code, so the same fp64 sums in the same order and the same merge.
+enum { POOL_HOST = 0, POOL_DEV = 1, POOL_RING = 2 };
+
+template <int KMAX, int QT, int RU, int POOL>
 __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a) {
     __shared__ WaveTile<QT> tile_s[ON_WAVES];
     __shared__ double wl_v[ON_WAVES][QT][KMAX];          // the K best of every wave, ranked against each other after the barrier
@@ -117,10 +124,15 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
     const int tid = threadIdx.x, lane = rat_lane(), wave = rat_wave();
     const int64_t ntiles = (a.Q + QT - 1) / QT;
     int64_t N = a.N, stride = a.N;
-    if constexpr (DEV) {
+    [[maybe_unused]] int64_t head = 0;
+    if constexpr (POOL != POOL_HOST) {
         stride = a.stride;
-        N = *a.n_dev;
+        N = a.n_dev[0];
         N = N < 0 ? 0 : (N > stride ? stride : N);
+    }
+    if constexpr (POOL == POOL_RING) {
+        head = a.n_dev[1];
+        head = head < 0 ? 0 : (head >= stride ? stride - 1 : head);
     }
     const int64_t chunk = (N + a.splits - 1) / a.splits;
     int parity = 0;
@@ -153,7 +165,12 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
 #pragma unroll
                 for (int u = 0; u < RU; ++u) {                                            // RU independent loads in flight per field
                     const int64_t n = n0 + (int64_t)u * ON_THREADS;
-                    id[u] = n < hi ? a.db_t[(int64_t)f * stride + n] : -1;
+                    int64_t slot = n;
+                    if constexpr (POOL == POOL_RING) {                                    // logical row -> its slot of the ring
+                        slot = n + head;
+                        slot = slot >= stride ? slot - stride : slot;
+                    }
+                    id[u] = n < hi ? a.db_t[(int64_t)f * stride + slot] : -1;
                 }
 #pragma unroll
                 for (int t = 0; t < QT; ++t) {
@@ -312,8 +329,9 @@ int64_t auto_splits(int64_t n_qry, int64_t n_db, int topk) {
     return s < 1 ? 1 : s;
 }
 
-// both entry points of the split scan: the same two launches, the scan instantiated with the row count by value or from the device
-template <bool DEV>
+// the three entry points of the split scan: the same two launches, the scan instantiated with the row count by value, from the device,
+// or with the ring's header from the device
+template <int POOL>
 int launch_split(const char* who, const int32_t* db_t, const int32_t* qry_ids, const double* qry_idf, double* out_values,
                  int64_t* out_indices, int64_t* out_lens, void* workspace, size_t workspace_bytes, int64_t n_db, const int64_t* n_dev,
                  int64_t stride, int64_t n_qry, int n_fields, int topk, int splits, void* stream) {
@@ -339,10 +357,10 @@ int launch_split(const char* who, const int32_t* db_t, const int32_t* qry_ids, c
     a.stride = stride;
     if (topk <= 8) {
         const int64_t items = (n_qry + 3) / 4 * splits;
-        RAT_LAUNCH((bm25_scan_split_kernel<8, 4, 4, DEV>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
+        RAT_LAUNCH((bm25_scan_split_kernel<8, 4, 4, POOL>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
     } else {
         const int64_t items = n_qry * splits;
-        RAT_LAUNCH((bm25_scan_split_kernel<32, 1, 4, DEV>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
+        RAT_LAUNCH((bm25_scan_split_kernel<32, 1, 4, POOL>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
     }
     if (rat_check_launch(who) != 0) return -1;
     RAT_LAUNCH(bm25_merge_kernel, (unsigned)(n_qry < 65536 ? n_qry : 65536), 64, 0, stream, a);
@@ -428,7 +446,7 @@ extern "C" int rat_bm25_topk_split(const int32_t* db_ids_field_major, const int3
             return rat_bm25_topk(db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, n_db, n_qry, n_fields, topk,
                                  stream);
     }
-    return launch_split<false>("rat_bm25_topk_split", db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
+    return launch_split<POOL_HOST>("rat_bm25_topk_split", db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
                                workspace_bytes, n_db, nullptr, n_db, n_qry, n_fields, topk, splits, stream);
 }
 
@@ -444,8 +462,22 @@ extern "C" int rat_bm25_topk_split_dev(const int32_t* db_ids_field_major, const 
     // the launch shape may not depend on the row count (a captured launch serves the pool after it has grown): the rule of
     // rat_bm25_topk_split applied to the CAPACITY; where it would hand over to the single-range kernel, one range through this one
     if (splits == 0) splits = (int)auto_splits(n_qry, capacity, topk);
-    return launch_split<true>("rat_bm25_topk_split_dev", db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
+    return launch_split<POOL_DEV>("rat_bm25_topk_split_dev", db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
                               workspace_bytes, 0, n_db_dev, capacity, n_qry, n_fields, topk, splits, stream);
+}
+
+extern "C" int rat_bm25_topk_split_ring(const int32_t* db_ids_field_major, const int64_t* header_dev, const int32_t* qry_ids,
+                                        const double* qry_idf, double* out_values, int64_t* out_indices, int64_t* out_lens,
+                                        void* workspace, size_t workspace_bytes, int64_t capacity, int64_t n_qry, int n_fields, int topk,
+                                        int splits, void* stream) {
+    RAT_REQUIRE(db_ids_field_major && header_dev && qry_ids && qry_idf && out_values && out_indices && out_lens, "null pointer");
+    RAT_REQUIRE(capacity > 0 && n_qry > 0 && n_fields > 0 && topk > 0, "bad dims");
+    RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
+    RAT_REQUIRE(topk <= ON_KMAX, "topK > 32 is not supported");
+    RAT_REQUIRE(splits >= 0 && splits <= ON_MAX_SPLITS, "splits must be 0 (library's choice) or 1..4096");
+    if (splits == 0) splits = (int)auto_splits(n_qry, capacity, topk);       // from the capacity, as rat_bm25_topk_split_dev
+    return launch_split<POOL_RING>("rat_bm25_topk_split_ring", db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens,
+                                   workspace, workspace_bytes, 0, header_dev, capacity, n_qry, n_fields, topk, splits, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------ growing the pool
@@ -508,4 +540,92 @@ extern "C" int rat_pool_append(const int32_t* ids, const float* labels, const in
     if (rat_check_launch("rat_pool_append") != 0) return -1;
     RAT_LAUNCH(pool_commit_kernel, 1u, 64, 0, stream, n_db_dev, n_rows, capacity);
     return rat_check_launch("rat_pool_append");
+}
+
+// ------------------------------------------------------------------------------------------------------------ a pool that slides
+// The same buffers as a ring: the header is {n, head}, logical row i lives in slot head + i (wrapped once).  A push that does not fit
+// overwrites the oldest rows — they leave the window in the tail launch, after the new rows are in place.
+namespace {
+
+struct RingHeader {
+    int64_t n, head;
+    bool ok;
+};
+// the header as both launches of a push and the evict read it; a header outside its domain (never written by these kernels) stops them
+__device__ __forceinline__ RingHeader ring_header(const int64_t* header, int64_t capacity) {
+    RingHeader h{header[0], header[1], false};
+    h.ok = h.n >= 0 && h.n <= capacity && h.head >= 0 && h.head < capacity;
+    return h;
+}
+__device__ __forceinline__ int64_t ring_wrap(int64_t slot, int64_t capacity) {     // slot < 2 capacity
+    return slot >= capacity ? slot - capacity : slot;
+}
+
+// pool_append_kernel's work items, every destination through the ring: row i of the batch goes to slot base + i (wrapped) with
+// base = head + n (wrapped) — the slot behind the newest row, which is the oldest row's once the window is full.  64 consecutive lanes
+// still write 64 consecutive slots of a column, in two pieces where the wrap falls among them; on the row-major side word r of the
+// batch goes to word base * L + r of pool_ids, wrapped at capacity * L.  AppendArgs::count is the two-word header here.
+__global__ void __launch_bounds__(256) pool_push_kernel(AppendArgs a) {
+    const RingHeader h = ring_header(a.count, a.capacity);
+    if (!h.ok || a.M > a.capacity) return;
+    const int64_t base = ring_wrap(h.head + h.n, a.capacity);
+    const int64_t nt = (int64_t)a.F * a.M;
+    const int64_t total = nt + (a.pool_ids ? a.M * a.L : 0);
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        if (e < nt) {
+            const int64_t f = e / a.M, i = e % a.M;
+            a.db_t[f * a.capacity + ring_wrap(base + i, a.capacity)] = a.ids[i * a.L + a.cols[f]];
+        } else {
+            const int64_t r = e - nt;
+            a.pool_ids[ring_wrap(base * a.L + r, a.capacity * a.L)] = a.ids[r];
+            if (r < a.M) a.pool_labels[ring_wrap(base + r, a.capacity)] = a.labels[r];
+        }
+    }
+}
+
+// the tail launch of a push: the E = max(0, n + M - capacity) oldest rows leave, the M new ones count
+__global__ void __launch_bounds__(64) pool_push_commit_kernel(int64_t* header, int64_t M, int64_t capacity) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        const RingHeader h = ring_header(header, capacity);
+        if (!h.ok || M > capacity) return;
+        const int64_t E = h.n + M > capacity ? h.n + M - capacity : 0;
+        header[1] = ring_wrap(h.head + E, capacity);
+        header[0] = h.n + M - E;
+    }
+}
+
+// the m oldest rows leave; the pool never becomes empty (a fresh index refuses an empty pool)
+__global__ void __launch_bounds__(64) pool_evict_kernel(int64_t* header, int64_t m, int64_t capacity) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        const RingHeader h = ring_header(header, capacity);
+        if (!h.ok || m < 0 || m >= h.n) return;
+        header[1] = ring_wrap(h.head + m, capacity);
+        header[0] = h.n - m;
+    }
+}
+
+}  // namespace
+
+extern "C" int rat_pool_push(const int32_t* ids, const float* labels, const int32_t* cols, int32_t* db_ids_field_major, int32_t* pool_ids,
+                             float* pool_labels, int64_t* header_dev, int64_t n_rows, int64_t capacity, int row_len, int n_fields,
+                             void* stream) {
+    RAT_REQUIRE(ids && cols && db_ids_field_major && header_dev, "null pointer");
+    RAT_REQUIRE((pool_ids == nullptr) == (pool_labels == nullptr), "pool_ids and pool_labels go together");
+    RAT_REQUIRE(pool_ids == nullptr || labels != nullptr, "null labels");
+    RAT_REQUIRE(n_rows > 0 && capacity > 0 && row_len > 0 && n_fields > 0, "bad dims");
+    RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
+    if (n_rows > capacity) return 0;                   // more rows than the window holds: nothing is written, the header stays
+    AppendArgs a{ids, labels, cols, db_ids_field_major, pool_ids, pool_labels, header_dev, n_rows, capacity, row_len, n_fields};
+    const int64_t blocks = (n_rows * (n_fields + (pool_ids ? row_len : 0)) + 255) / 256;
+    RAT_LAUNCH(pool_push_kernel, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
+    if (rat_check_launch("rat_pool_push") != 0) return -1;
+    RAT_LAUNCH(pool_push_commit_kernel, 1u, 64, 0, stream, header_dev, n_rows, capacity);
+    return rat_check_launch("rat_pool_push");
+}
+
+extern "C" int rat_pool_evict(int64_t* header_dev, int64_t n_rows, int64_t capacity, void* stream) {
+    RAT_REQUIRE(header_dev, "null pointer");
+    RAT_REQUIRE(capacity > 0, "bad dims");
+    RAT_LAUNCH(pool_evict_kernel, 1u, 64, 0, stream, header_dev, n_rows, capacity);
+    return rat_check_launch("rat_pool_evict");
 }

@@ -159,6 +159,11 @@ _SIGNATURES = {
     "rat_pool_append": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int, c_int, _P]),
     "rat_bm25_topk_split_dev": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_size_t, c_int64, c_int64, c_int, c_int, c_int, _P]),
     "rat_batch_assemble_dev": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, _P]),
+    # a pool that slides: the same buffers as a ring, header {row count, slot of the oldest row} in device memory
+    "rat_pool_push": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int, c_int, _P]),
+    "rat_pool_evict": (c_int, [_P, c_int64, c_int64, _P]),
+    "rat_bm25_topk_split_ring": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_size_t, c_int64, c_int64, c_int, c_int, c_int, _P]),
+    "rat_batch_assemble_ring": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_int, c_int, c_int, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

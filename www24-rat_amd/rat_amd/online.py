@@ -20,9 +20,19 @@ float64 ``log``: the index keeps the per-column (distinct ids, counts) on the ho
 tables into the same device buffers.  After ``append`` the object answers exactly like a fresh one over ``concatenate([pool, rows])``.
 Without ``capacity`` nothing changes: the immutable index, the same kernels and launches as before.
 
+The pool can slide.  ``capacity=C, window=True`` uses the same buffers as a ring: the device header is two words, the live row count
+and ``head``, the physical slot of the oldest live row.  ``append(rows)`` never refuses for lack of room — when the window is full the
+oldest rows leave in the same call (``rat_pool_push``) — and ``evict(m)`` drops the m oldest (``rat_pool_evict``).  Everything a
+request sees is LOGICAL (0 = the oldest live row): the indices ``retrieve`` returns, the tie rule (the older row wins), the row a
+``-1`` padding resolves to (the newest).  The scan and the assembly map a logical row to its slot on the device
+(``rat_bm25_topk_split_ring``, ``rat_batch_assemble_ring``) from that header, so captured request graphs survive appends and evictions
+alike, and at any moment the object answers exactly like a fresh one over the live rows in age order.  The index keeps the used columns
+of the live rows in a host ring to know which ids leave; an id whose count reaches zero leaves its column's table.
+Without ``window`` a pool with ``capacity`` is append-only and refuses rows when it is full.
+
 Not served online (refused at construction): exact-match columns (numbering the groups needs a host ``np.unique`` over pool and
-queries), label-wise retrieval, topK > 32, more than 32 retrieval columns, data-parallel models.  The pool is append-only: rows are
-never evicted or deleted (a pool that shrinks is a new ``RetrievalIndex``).
+queries), label-wise retrieval, topK > 32, more than 32 retrieval columns, data-parallel models.  Rows leave oldest first only: there
+is no deletion of an arbitrary row (a pool that loses other rows is a new ``RetrievalIndex``).
 """
 import numpy as np
 import torch
@@ -69,9 +79,15 @@ class RetrievalIndex:
     ``capacity`` (>= len(pool)): the buffers are allocated for that many rows, once, and ``append(rows)`` adds rows in place; the
     index then equals a fresh one over the concatenated pool.  Append-only (no eviction, no deletion).  Memory: ``db_t`` is
     4 F capacity bytes; column f's IDF table is reserved for (its distinct ids now + capacity - len(pool)) entries of 12 bytes — every
-    appended row adds at most one distinct id per column."""
+    appended row adds at most one distinct id per column.
 
-    def __init__(self, pool_array, col_indices, topK, device, lib=None, exact_match_col_indices=None, splits=0, capacity=None):
+    ``window=True`` (needs ``capacity``): the buffers are a ring over the most recent rows.  ``append`` evicts the oldest rows when
+    they do not fit, ``evict(m)`` drops the m oldest; the index then equals a fresh one over the live rows, oldest first.  Memory:
+    ``db_t`` is 4 F capacity bytes as before; a column can hold up to capacity distinct ids at some time, so every column's IDF table
+    is reserved in full — 12 F capacity bytes, three times ``db_t`` — and the host keeps 8 F capacity bytes of the live rows' ids."""
+
+    def __init__(self, pool_array, col_indices, topK, device, lib=None, exact_match_col_indices=None, splits=0, capacity=None,
+                 window=False):
         if exact_match_col_indices:
             raise ValueError("online retrieval does not support exact-match columns (exact_match_col_indices=%s): numbering the groups "
                              "needs a host pass over pool and queries" % (list(exact_match_col_indices),))
@@ -93,6 +109,9 @@ class RetrievalIndex:
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)        # noqa: E731
         self.n_db = len(db)
         self.capacity = None
+        self.window = bool(window)
+        if self.window and capacity is None:
+            raise ValueError("window=True needs capacity= (the number of rows the sliding window holds)")
         self._col_list = cols
         self.cols = up(np.asarray(cols, dtype=np.int32))
         if capacity is not None:
@@ -105,13 +124,17 @@ class RetrievalIndex:
         self.table_offsets = up(np.concatenate([[0], np.cumsum([len(v) for v, _ in tables])]).astype(np.int64))
 
     def retrieve(self, ids):
-        """ids [B, L] (full encoded rows) -> (values fp64 [B, K], indices int64 [B, K] with -1 padding, lens int64 [B]), on the device"""
+        """ids [B, L] (full encoded rows) -> (values fp64 [B, K], indices int64 [B, K] with -1 padding, lens int64 [B]), on the device.
+        With ``window=True`` the indices are LOGICAL positions (0 = the oldest live row, len(index) - 1 = the newest): they hold until
+        the next eviction (an ``evict``, or an ``append`` into a full window), which renumbers the rows."""
         ids = _as_device_ids(ids, self.device)
         if ids.shape[1] != self.row_len:
             raise ValueError("ids have %d columns, the pool's rows have %d" % (ids.shape[1], self.row_len))
         if ids.shape[0] == 0:
             raise ValueError("empty request")
         qry_ids, qry_idf = ops.bm25_query_prepare(ids, self.cols, self.table_ids, self.table_idf, self.table_offsets, lib=self._lib)
+        if self.window:
+            return ops.bm25_topk_split_ring(self.db_t, self.count, qry_ids, qry_idf, self.topK, splits=self.splits, lib=self._lib)
         if self.capacity is not None:
             return ops.bm25_topk_split_dev(self.db_t, self.count, qry_ids, qry_idf, self.topK, splits=self.splits, lib=self._lib)
         return ops.bm25_topk_split(self.db_t, qry_ids, qry_idf, self.topK, splits=self.splits, lib=self._lib)
@@ -127,10 +150,16 @@ class RetrievalIndex:
         self.capacity = capacity
         self.db_t = torch.zeros((F, capacity), dtype=torch.int32, device=dev)
         self.db_t[:, :n] = torch.from_numpy(np.ascontiguousarray(retrieval._as_int32(db, "pool").T)).to(dev)
-        self.count = torch.full((1,), n, dtype=torch.int64, device=dev)        # the header the kernels read the row count from
+        # the header the kernels read the row count from; a window's has a second word, the slot of the oldest live row
+        self.count = torch.tensor([n, 0] if self.window else [n], dtype=torch.int64, device=dev)
         # host mirror of the tables' integer half: per column (sorted distinct ids, counts); the weights are derived from it
         self._counts = [np.unique(db[:, c], return_counts=True) for c in range(F)]
         table_cap = sum(len(v) for v, _ in self._counts) + F * (capacity - n)
+        if self.window:                                                        # any column may hold `capacity` distinct ids some day
+            table_cap = F * capacity
+            self._ring = np.zeros((capacity, F), dtype=db.dtype)               # used columns of the live rows, slot-major: who leaves
+            self._ring[:n] = db
+            self._head = 0
         self.table_ids = torch.zeros(table_cap, dtype=torch.int32, device=dev)
         self.table_idf = torch.zeros(table_cap, dtype=torch.float64, device=dev)
         self.table_offsets = torch.zeros(F + 1, dtype=torch.int64, device=dev)
@@ -150,25 +179,85 @@ class RetrievalIndex:
     def append(self, rows, _pool_ids=None, _pool_labels=None):
         """rows [M, L + 1] (label last; numpy, host or device tensor) become pool rows n .. n + M - 1: retrievable by the next request,
         and every IDF weight moves (N and the counts).  Ordered with the requests on the current stream.  ValueError — and nothing
-        written — for an index without ``capacity``, rows that do not fit, a wrong column count or an id outside int32."""
+        written — for an index without ``capacity``, rows that do not fit, a wrong column count or an id outside int32.
+        With ``window=True`` rows always fit: the len(index) + M - capacity oldest rows leave in the same call (only M > capacity is
+        refused), and every logical index moves down by that many."""
         if self.capacity is None:
             raise ValueError("this index was built without capacity: its pool is immutable (pass capacity= to append rows)")
         ids32, as_int, labels = _host_rows(rows, self.row_len)
         M = len(ids32)
+        if self.window:
+            return self._push(ids32, as_int, labels, _pool_ids, _pool_labels)
         if self.n_db + M > self.capacity:
             raise ValueError("appending %d rows to %d exceeds the capacity of %d rows" % (M, self.n_db, self.capacity))
-        for f, c in enumerate(self._col_list):                                 # np.unique over the M new rows only
-            vals, counts = self._counts[f]
-            u, uc = np.unique(as_int[:, c], return_counts=True)
-            pos = np.searchsorted(vals, u)
-            hit = vals[np.minimum(pos, len(vals) - 1)] == u
-            counts = counts.copy()
-            counts[pos[hit]] += uc[hit]
-            self._counts[f] = (np.insert(vals, pos[~hit], u[~hit]), np.insert(counts, pos[~hit], uc[~hit]))
+        self._count_in(as_int[:, self._col_list])
         self.n_db += M
         dev = self.device
         ops.pool_append(torch.from_numpy(ids32).to(dev), torch.from_numpy(labels).to(dev), self.cols, self.db_t, self.count,
                         _pool_ids, _pool_labels, lib=self._lib)
+        self._upload_tables()
+
+    def _count_in(self, used):
+        """used [M, F] (the used columns of rows coming in) -> the mirrored (distinct ids, counts): np.unique over the M rows only"""
+        for f in range(used.shape[1]):
+            vals, counts = self._counts[f]
+            u, uc = np.unique(used[:, f], return_counts=True)
+            pos = np.searchsorted(vals, u)
+            hit = vals[np.minimum(pos, len(vals) - 1)] == u if len(vals) else np.zeros(len(u), dtype=bool)
+            counts = counts.copy()
+            counts[pos[hit]] += uc[hit]
+            self._counts[f] = (np.insert(vals, pos[~hit], u[~hit]), np.insert(counts, pos[~hit], uc[~hit]))
+
+    # ---- the sliding form ----------------------------------------------------------------------------------------------
+    def _slots(self, first, m):
+        """physical slots of the logical rows first .. first + m - 1"""
+        return (self._head + first + np.arange(m)) % self.capacity
+
+    def _count_out(self, m):
+        """the m oldest rows leave the mirrored counts; an id nobody holds any more leaves its column's table, as a fresh index over
+        the remaining rows would not hold it (a request whose first row carries it then MISSES: the dtype rule of
+        rat_bm25_query_prepare depends on that)"""
+        gone = self._ring[self._slots(0, m)]
+        for f in range(gone.shape[1]):
+            vals, counts = self._counts[f]
+            u, uc = np.unique(gone[:, f], return_counts=True)
+            counts = counts.copy()
+            counts[np.searchsorted(vals, u)] -= uc
+            keep = counts > 0
+            self._counts[f] = (vals[keep], counts[keep])
+        self._head = (self._head + m) % self.capacity
+        self.n_db -= m
+
+    def _push(self, ids32, as_int, labels, pool_ids, pool_labels):
+        M = len(ids32)
+        if M > self.capacity:
+            raise ValueError("appending %d rows exceeds the capacity of the window (%d rows)" % (M, self.capacity))
+        E = max(0, self.n_db + M - self.capacity)
+        if E:
+            self._count_out(E)
+        used = as_int[:, self._col_list]
+        self._count_in(used)
+        self._ring[self._slots(self.n_db, M)] = used
+        self.n_db += M
+        dev = self.device
+        ops.pool_push(torch.from_numpy(ids32).to(dev), torch.from_numpy(labels).to(dev), self.cols, self.db_t, self.count,
+                      pool_ids, pool_labels, lib=self._lib)
+        self._upload_tables()
+
+    def evict(self, m):
+        """The m oldest rows leave the window (``window=True`` only): every IDF weight moves (N and the counts), ids nobody holds any
+        more leave the tables, and every logical index moves down by m.  Ordered with the requests on the current stream.
+        ValueError — and nothing written — for m < 0 or m >= len(index): the pool never becomes empty."""
+        if not self.window:
+            raise ValueError("this index was built without window=True: rows cannot be evicted")
+        m = int(m)
+        if m < 0 or m >= self.n_db:
+            raise ValueError("evict(%d) on a window of %d rows: 0 <= m < len(index) is required (the pool never becomes empty)"
+                             % (m, self.n_db))
+        if m == 0:
+            return
+        self._count_out(m)
+        ops.pool_evict(self.count, m, self.capacity, lib=self._lib)
         self._upload_tables()
 
 
@@ -196,13 +285,15 @@ class OnlineScorer:
     ``used_col_indices``, ...).  ``graph=True``: after ``graph_warmup`` eager requests of a batch size (<= ``graph_max_batch``) the
     chain is captured and replayed; the weights are read at replay time, so the graph survives optimizer steps and load_state_dict.
     ``capacity``: room for that many pool rows; ``append(rows)`` then adds labelled rows in place and the captured graphs stay valid
-    (they read the row count from device memory).  Append-only."""
+    (they read the row count from device memory).  Append-only, unless ``window=True``: the pool is then a sliding window over the most
+    recent ``capacity`` rows — ``append`` evicts the oldest rows when the new ones do not fit, ``evict(m)`` drops the m oldest, and the
+    captured graphs stay valid through both."""
 
     graph_warmup = 2
     graph_max_batch = 4096
     graph_sizes = 16               # at most this many request sizes get a graph; others stay eager
 
-    def __init__(self, model, pool_array, retrieval_configs, graph=True, lib=None, capacity=None):
+    def __init__(self, model, pool_array, retrieval_configs, graph=True, lib=None, capacity=None, window=False):
         cfg = retrieval_configs
         if cfg.get("exact_match_col_indices") or cfg.get("exact_match_cols"):
             raise ValueError("online scoring does not support exact-match columns (exact_match_cols / exact_match_col_indices are set)")
@@ -216,7 +307,7 @@ class OnlineScorer:
         self.model = model
         self.device = model.device
         self._lib = lib or model._lib
-        self.index = RetrievalIndex(pool_array, cols, cfg["topK"], self.device, lib=self._lib, capacity=capacity)
+        self.index = RetrievalIndex(pool_array, cols, cfg["topK"], self.device, lib=self._lib, capacity=capacity, window=window)
         pool_array = np.asarray(pool_array)
         self.pool_ids = torch.from_numpy(np.ascontiguousarray(pool_array[:, :-1].astype(np.int32))).to(self.device)
         self.pool_labels = torch.from_numpy(np.ascontiguousarray(pool_array[:, -1].astype(np.float32))).to(self.device)
@@ -243,6 +334,8 @@ class OnlineScorer:
         rows, labels = self._constants(ids.shape[0])
         _values, indices, _lens = self.index.retrieve(ids)
         # the request is the query table, the kernel's own index output the neighbour lists; -1 keeps its numpy meaning, as offline
+        if self.index.window:                                                  # ... logical positions in the ring, -1 its newest row
+            return ops.batch_assemble_ring(ids, labels, self.pool_ids, self.pool_labels, indices, rows, self.index.count, lib=self._lib)
         if self.index.capacity is not None:                                    # ... counted back from the pool's last LIVE row
             return ops.batch_assemble_dev(ids, labels, self.pool_ids, self.pool_labels, indices, rows, self.index.count, lib=self._lib)
         return ops.batch_assemble(ids, labels, self.pool_ids, self.pool_labels, indices, rows, lib=self._lib)
@@ -253,8 +346,14 @@ class OnlineScorer:
 
     def append(self, rows):
         """``RetrievalIndex.append`` plus the row store (ids and labels of the new rows, the same launch).  Afterwards the scorer equals
-        ``OnlineScorer(model, np.concatenate([pool, rows]), cfg)``; captured request graphs are kept and serve the grown pool."""
+        ``OnlineScorer(model, np.concatenate([pool, rows]), cfg)``; captured request graphs are kept and serve the grown pool.
+        With ``window=True``: over the last ``capacity`` rows of that concatenation."""
         self.index.append(rows, self.pool_ids, self.pool_labels)
+
+    def evict(self, m):
+        """``RetrievalIndex.evict``: the m oldest pool rows leave (``window=True`` only).  Afterwards the scorer equals a fresh one over
+        the remaining rows; captured request graphs are kept."""
+        self.index.evict(m)
 
     def batch(self, ids):
         """-> data.DeviceBatch (idx [B, 1 + K, L], label_ids [B, 1 + K], y_true = zeros): what the model's forward consumes"""

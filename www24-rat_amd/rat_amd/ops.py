@@ -1013,3 +1013,66 @@ def batch_assemble_dev(data_ids, data_labels, pool_ids, pool_labels, retr_indice
     lib.call("rat_batch_assemble_dev", _p(data_ids), _p(data_labels), _p(pool_ids), _p(pool_labels), _p(retr_indices), _p(rows),
              _p(idx), _p(label_ids), _p(y_true), Q, _p(count), B, K, L, _stream(data_ids))
     return idx, label_ids, y_true
+
+
+# ----------------------------------------------------------------------------- a pool that slides: the same buffers as a ring
+def pool_push(ids, labels, cols, db_t, header, pool_ids=None, pool_labels=None, lib=None):
+    """pool_append into a ring: header = [n, head] (int64, device); row i goes to slot head + n + i (wrapped) of db_t, pool_ids and
+    pool_labels, the max(0, n + M - capacity) oldest rows leave, all on the device.  M > capacity writes nothing."""
+    lib = lib or get_lib()
+    _chk(ids, torch.int32, "ids"), _chk(labels, name="labels"), _chk(cols, torch.int32, "cols"), _chk(db_t, torch.int32, "db_t")
+    _chk(header, torch.int64, "header"), _chk(pool_ids, torch.int32, "pool_ids"), _chk(pool_labels, name="pool_labels")
+    M, L = ids.shape
+    F, capacity = db_t.shape
+    assert cols.numel() == F and labels.numel() == M and header.numel() >= 2 and (pool_ids is None) == (pool_labels is None)
+    if pool_ids is not None:
+        assert tuple(pool_ids.shape) == (capacity, L) and pool_labels.numel() == capacity
+    lib.call("rat_pool_push", _p(ids), _p(labels), _p(cols), _p(db_t), _p(pool_ids), _p(pool_labels), _p(header), M, capacity, L, F,
+             _stream(db_t))
+
+
+def pool_evict(header, m, capacity, lib=None):
+    """the m oldest rows of a ring leave: header = [n, head] (int64, device) -> [n - m, head + m wrapped]; m < 0 or m >= n: nothing"""
+    lib = lib or get_lib()
+    _chk(header, torch.int64, "header")
+    assert header.numel() >= 2
+    lib.call("rat_pool_evict", _p(header), int(m), int(capacity), _stream(header))
+
+
+def bm25_topk_split_ring(db_t, header, qry_ids, qry_idf, topk, splits=0, lib=None):
+    """bm25_topk_split over the header[0] live rows of the ring db_t int32 [F, capacity], oldest (slot header[1]) first; the indices
+    returned are logical positions; splits = 0: chosen from the capacity"""
+    lib = lib or get_lib()
+    _chk(db_t, torch.int32, "db_t"), _chk(qry_ids, torch.int32, "qry_ids"), _chk(qry_idf, torch.float64, "qry_idf")
+    _chk(header, torch.int64, "header")
+    F, capacity = db_t.shape
+    Q = qry_ids.shape[0]
+    assert tuple(qry_ids.shape) == (Q, F) and tuple(qry_idf.shape) == (Q, F) and header.numel() >= 2
+    dev = db_t.device
+    nbytes = lib.size("rat_bm25_topk_split_workspace", Q, int(topk), int(splits))
+    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    out_v = torch.empty((Q, topk), dtype=torch.float64, device=dev)
+    out_i = torch.empty((Q, topk), dtype=torch.int64, device=dev)
+    out_l = torch.empty((Q,), dtype=torch.int64, device=dev)
+    lib.call("rat_bm25_topk_split_ring", _p(db_t), _p(header), _p(qry_ids), _p(qry_idf), _p(out_v), _p(out_i), _p(out_l), _p(ws),
+             ws.numel() * 8, capacity, Q, F, int(topk), int(splits), _stream(db_t))
+    return out_v, out_i, out_l
+
+
+def batch_assemble_ring(data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, header, lib=None):
+    """batch_assemble against a ring pool (pool_ids [capacity, L], header = [n, head] int64 on the device): neighbour indices are
+    logical positions, a negative one counts back from n"""
+    lib = lib or get_lib()
+    _chk(data_ids, torch.int32, "data_ids"), _chk(pool_ids, torch.int32, "pool_ids")
+    _chk(data_labels, name="data_labels"), _chk(pool_labels, name="pool_labels")
+    _chk(retr_indices, torch.int64, "retr_indices"), _chk(rows, torch.int64, "rows"), _chk(header, torch.int64, "header")
+    Q, L = data_ids.shape
+    K, B = retr_indices.shape[1], rows.numel()
+    assert header.numel() >= 2 and pool_ids.shape[1] == L and pool_labels.numel() == pool_ids.shape[0]
+    dev = data_ids.device
+    idx = torch.empty((B, K + 1, L), dtype=torch.int32, device=dev)
+    label_ids = torch.empty((B, K + 1), dtype=torch.int32, device=dev)
+    y_true = torch.empty((B,), dtype=torch.float32, device=dev)
+    lib.call("rat_batch_assemble_ring", _p(data_ids), _p(data_labels), _p(pool_ids), _p(pool_labels), _p(retr_indices), _p(rows),
+             _p(idx), _p(label_ids), _p(y_true), Q, _p(header), int(pool_ids.shape[0]), B, K, L, _stream(data_ids))
+    return idx, label_ids, y_true
