@@ -25,6 +25,7 @@
 #include "rat_device.h"
 #include "../../include/rat_hip.h"
 
+#include <atomic>
 #include <cstdlib>
 #include <initializer_list>
 
@@ -1216,6 +1217,18 @@ static int b3_fwd_matrix_core(int L, int nq) {
     if (k != 2 && !((L >= 28 && L <= 32) || L >= 40)) return 0;
     return L > 32 ? 3 : (L > 16 ? 2 : 1);
 }
+// attn_fwd3_2wg_kernel instead of attn_fwd3_kernel<false> / <true> (the caller has checked the geometry: embedding_dim 64, 8 heads x 10, VALU
+// core, every position a query).  attn_fwd_2wg knob: 1 / 0 force it on / off; -1 (default): on, at every length — there is no rule by length.
+// Same-box A/B against the parent commit's library, three interleaved rounds (profiles/attn_fwd_2wg/ab.txt): per launch in the north-star step
+// L = 21 0.547 -> 0.486 ms (-11 %), L = 11 0.507 -> 0.446 ms (-12 %); the eval forward 5.14 -> 4.65 ms (-9.4 %); the step 18.39 -> 18.07 ms
+// (-1.7 %: the parent's three rounds lie within 0.08 %, but the SAME kernel code forced by the knob spread 1.09 % and the new form 1.36 %, so
+// on the step the gain is under three times those; its slowest round is faster than the fastest round of either).  It wins at both lengths
+// measured, with five and with three sequences per chunk; the other lengths of the VALU core (L < 28, 33 ... 39) take it on the strength of
+// that — they have not been measured one by one.
+static bool b3_fwd_two_groups() { return rat_knob(RAT_KNOB_ATTN_FWD_2WG) != 0; }
+// diagnostic hook (not part of include/rat_hip.h): launches of attn_fwd3_2wg_kernel by this process so far — lets a test tell which form ran
+static std::atomic<long long> g_fwd3_2wg_launches{0};
+extern "C" long long rat_debug_attn_fwd_2wg_launches(void) { return g_fwd3_2wg_launches.load(std::memory_order_relaxed); }
 static bool b3_ph_enabled() {                          // on unless the attn_bwd_ph knob is 0 (same-box A/B: L = 11 1.2477 -> 1.2322 ms, -1.2 %)
     return rat_knob(RAT_KNOB_ATTN_BWD_PH) != 0;
 }
@@ -1299,6 +1312,7 @@ extern "C" int rat_attn_fwd_ex(const float* x, const float* res, float* y, float
         W.qkv = RatWPlanes{reinterpret_cast<const rat_u4*>(p_qkv), 2};
         W.out = RatWPlanes{reinterpret_cast<const rat_u4*>(p_out), 3};
         const unsigned b3_blocks = (unsigned)(a.nchunks < rat_max_blocks() ? a.nchunks : rat_max_blocks());
+        const unsigned b3_blocks2 = (unsigned)(a.nchunks < 2 * rat_max_blocks() ? a.nchunks : 2 * rat_max_blocks());   // two work-groups per CU
         if (heads == 4) {                                        // 4 heads x 20 (RAT_m3): one general instantiation
             RAT_LAUNCH((attn_fwd3_kernel<true, false, false, false, 0, 4>), b3_blocks, ATT_THREADS, b3_fwd_smem(), stream, a, W);
             return rat_check_launch("rat_attn_fwd (bf16x3, 4 heads)");
@@ -1314,11 +1328,19 @@ extern "C" int rat_attn_fwd_ex(const float* x, const float* res, float* y, float
             RAT_LAUNCH((attn_fwd3_kernel<false, false, false, false, 2>), b3_blocks, ATT_THREADS, b3_fwd_smem(), stream, a, W);
         else if (plain && b3_fwd_matrix_core(a.L, a.nq) == 1)      // (sequences of at most 16 tokens: only when the knob forces it)
             RAT_LAUNCH((attn_fwd3_kernel<false, false, false, false, 1>), b3_blocks, ATT_THREADS, b3_fwd_smem(), stream, a, W);
+        else if (plain && b3_fwd_two_groups()) {
+            RAT_LAUNCH((attn_fwd3_2wg_kernel<false>), b3_blocks2, ATT_THREADS, b3_fwd2_smem(), stream, a, W);
+            g_fwd3_2wg_launches.fetch_add(1, std::memory_order_relaxed);
+        }
         else if (plain) RAT_LAUNCH((attn_fwd3_kernel<false>), b3_blocks, ATT_THREADS, b3_fwd_smem(), stream, a, W);
         else if (b3_fwd_matrix_core(a.L, a.L) == 3)                // (EX computes every position whatever `queries` says)
             RAT_LAUNCH((attn_fwd3_kernel<true, false, false, false, 3>), b3_blocks, ATT_THREADS, b3_fwd_smem(), stream, a, W);
         else if (b3_fwd_matrix_core(a.L, a.L) == 2)
             RAT_LAUNCH((attn_fwd3_kernel<true, false, false, false, 2>), b3_blocks, ATT_THREADS, b3_fwd_smem(), stream, a, W);
+        else if (b3_fwd_two_groups()) {
+            RAT_LAUNCH((attn_fwd3_2wg_kernel<true>), b3_blocks2, ATT_THREADS, b3_fwd2_smem(), stream, a, W);
+            g_fwd3_2wg_launches.fetch_add(1, std::memory_order_relaxed);
+        }
         else RAT_LAUNCH((attn_fwd3_kernel<true>), b3_blocks, ATT_THREADS, b3_fwd_smem(), stream, a, W);   // (computes every position)
         return rat_check_launch("rat_attn_fwd (bf16x3)");
     }

@@ -30,6 +30,14 @@ constexpr size_t B3_W_QKV = (size_t)15 * 2 * 3 * 1024, B3_W_OUT = (size_t)4 * 3 
                  B3_W_QKVT = (size_t)4 * 8 * 3 * 1024;
 constexpr size_t B3_W_BYTES = B3_W_QKV + B3_W_OUT + B3_W_OUTT + B3_W_QKVT;
 
+// ---- forward.  Two LDS layouts:
+//   attn_fwd3_kernel (every instantiation), bytes: [x planes 24576; later the fp32 staging tile][Q|K|V fp32 [64][244] 62464; O replaces Q]
+//     [O planes 30912][row maps 1024][lse 2048][W_out fragment planes 36864] = 157888: one work-group of 8 waves per CU, 157-167 VGPRs;
+//   attn_fwd3_2wg_kernel (embedding_dim 64, 8 heads x 10, VALU core, every position a query — what the north-star step launches),
+//     bytes: [x planes -> fp32 Q / O [64][84] -> staging tile 24576][K|V fp32 [64][164] -> O planes 41984][row maps, lse, gamma | beta 3584]
+//     = 70144, 124-126 VGPRs: two work-groups per CU, one's MFMA phases and chunk-top loads under the other's VALU core (see the comment
+//     above that kernel).  Per launch 0.547 -> 0.486 ms at L = 21 and 0.507 -> 0.446 ms at L = 11 (profiles/attn_fwd_2wg/ab.txt); the host's
+//     rule is b3_fwd_two_groups in attn.hip, the attn_fwd_2wg knob forces either form.
 constexpr size_t B3_FWD_LSE = (size_t)3 * B3_XP + (size_t)64 * B3_LDQ * 4 + (size_t)3 * B3_OP + 2 * 64 * 8;   // [64][8] log-sum-exp of the chunk
 constexpr size_t B3_FWD_WOUT = B3_FWD_LSE + (size_t)64 * B3_H * 4;      // the output projection's fragment planes, LDS-resident (36 KB)
 constexpr size_t b3_fwd_smem() { return B3_FWD_WOUT + B3_W_OUT; }
@@ -514,6 +522,266 @@ __global__ void __launch_bounds__(ATT_THREADS) attn_fwd3_kernel(AttnArgs a, Attn
                 const float4 t1 = *reinterpret_cast<const float4*>(ys + (size_t)r * LDY + 8 * sb + 4);
                 *reinterpret_cast<float4*>(a.y + tok * dreal + 8 * sb) = make_float4(t0.x + x0.x, t0.y + x0.y, t0.z + x0.z, t0.w + x0.w);
                 *reinterpret_cast<float4*>(a.y + tok * dreal + 8 * sb + 4) = make_float4(t1.x + x1.x, t1.y + x1.y, t1.z + x1.z, t1.w + x1.w);
+            }
+        }
+        __syncthreads();
+#ifndef RAT_EMU
+        asm volatile("" ::"v"(pf));
+#endif
+        RAT_PROF_MARK(5);
+    }
+    RAT_PROF_FLUSH(a.prof, 48);
+}
+
+// ---- the forward in 69 KB of LDS and 128 VGPRs: TWO work-groups per CU (attn_fwd3_2wg_kernel) ------------------------------------------
+// One chunk of attn_fwd3_kernel runs through strictly serial phases on different pipes (LayerNorm: VALU, Q|K|V: MFMA, core: VALU, O -> planes:
+// VALU, projection: MFMA), and its 157 KB of LDS keep a second work-group off the CU: the matrix pipe idles under the core, and the other way
+// round.  This form serves the instantiations the north-star step launches — embedding_dim 64, 8 heads x 10, the VALU core, every position a
+// query: <false> and <true> of attn_fwd3_kernel — with the SAME per-element arithmetic (K-step order of the GEMMs, softmax loop, split,
+// Dropout indexing: y, o_save and lse_save are bit-identical, tests/test_gpu_attn_fwd_2wg.py), in regions that are reused as they die:
+//   R0 [0, 24576)       LayerNorm(x) planes  ->  fp32 Q [64][84] (O replaces Q in place)  ->  the projection's fp32 staging tile [64][68]
+//   R1 [24576, 66560)   fp32 K|V [64][164]   ->  O planes (3 x 10304)
+//   [66560, 70144)      row maps (2 x 64 x 8), log-sum-exp [64][8], LayerNorm gamma | beta
+//   * Q over the x planes: b3_gemm_rows_release reads ALL of a wave's A fragments before its first MFMA; one work-group barrier behind
+//     those reads and the planes are dead.  Column tiles 0 ... 4 (Q) go to R0, 5 ... 14 (K|V) to R1; the dealing of tiles to waves is that
+//     of b3_gemm_rows.
+//   * O -> planes reads R0 and writes R1 (dead behind the core's closing barrier): source and destination never overlap.  The planes' slack
+//     (the padded third K step of row 63) lies over old K|V bits and is zeroed with them: it meets zero weight planes, and 0 x NaN is NaN.
+//   * W_out's fragments come from L2 (as in the GRP form): nothing else could give up 36 KB.
+//   * gamma / beta live in LDS instead of 16 registers (as in the backward).
+// The grid is 2 x rat_max_blocks() work-groups.  The host selects this form through b3_fwd_two_groups (attn.hip; knob attn_fwd_2wg).
+constexpr int B3_LDQ2 = B3_I + 4;                       // fp32 Q / O tile row (floats); 84 = 244 mod 32: the core's Q / O accesses keep their bank pattern
+constexpr int B3_LDK2 = 2 * B3_I + 4;                   // fp32 K|V tile row: 164 = 4 mod 32 where 244 is 20 — the K / V reads of the core (a wave's lanes
+//                                                         share few (sequence, key) rows and differ by head, 10 floats apart) DO change banks; covered by the A/B
+constexpr size_t B3_F2_KV = (size_t)3 * B3_XP, B3_F2_MAP = B3_F2_KV + (size_t)64 * B3_LDK2 * 4, B3_F2_LSE = B3_F2_MAP + 2 * 64 * 8,
+                 B3_F2_LN = B3_F2_LSE + (size_t)64 * B3_H * 4;
+constexpr size_t b3_fwd2_smem() { return B3_F2_LN + 2 * B3_D * 4; }
+static_assert(b3_fwd2_smem() <= 80 * 1024, "LDS budget (forward, two work-groups per CU)");
+static_assert((size_t)64 * B3_LDQ2 * 4 <= B3_F2_KV && (size_t)64 * (B3_D + 4) * 4 <= B3_F2_KV, "fp32 Q / the staging tile overlay the x planes");
+static_assert((size_t)3 * B3_OP <= (size_t)64 * B3_LDK2 * 4, "the O planes overlay the K|V tile");
+
+// b3_gemm_rows (REV = false) with a work-group barrier between the A reads and the first MFMA: behind it the planes of A may be overwritten
+// (by the epilogue, too).  Every wave must arrive: n_tiles >= 4.
+template <int KS, class PA, class BW, class Epi>
+__device__ __forceinline__ void b3_gemm_rows_release(const PA& A, const BW& Bw, int n_tiles, const Epi& epi) {
+    const int w = rat_wave(), mt0 = 2 * (w >> 2);
+    int nt = w & 3;
+    RatB3 b = Bw(nt, 0);
+    RatB3 a[2][KS];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int s = 0; s < KS; ++s) a[i][s] = A.row_frag(mt0 + i, s);
+    __syncthreads();
+    for (; nt < n_tiles; nt += 4) {
+        f32x4 acc[2] = {rat_zero4(), rat_zero4()};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const bool last = s == KS - 1;
+            const RatB3 bn = Bw(last ? (nt + 4 < n_tiles ? nt + 4 : nt) : nt, last ? 0 : s + 1);
+            const RatB3 as[2] = {a[0][s], a[1][s]};
+            rat_mfma3_block<2>(acc, as, b);
+            b = bn;
+        }
+        epi(mt0, nt, acc[0]);
+        epi(mt0 + 1, nt, acc[1]);
+    }
+}
+
+// b3_gemm_rows with the A fragments read K step by K step (24 instead of 24 KS registers; the same MFMAs in the same order): what lets the
+// output projection's three K steps fit the 128-register budget
+template <int KS, class PA, class BW, class Epi>
+__device__ __forceinline__ void b3_gemm_rows_stream(const PA& A, const BW& Bw, int n_tiles, const Epi& epi) {
+    const int w = rat_wave(), mt0 = 2 * (w >> 2);
+    int nt = w & 3;
+    if (nt >= n_tiles) return;
+    RatB3 b = Bw(nt, 0);
+    for (; nt < n_tiles; nt += 4) {
+        f32x4 acc[2] = {rat_zero4(), rat_zero4()};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const bool last = s == KS - 1;
+            const RatB3 bn = Bw(last ? (nt + 4 < n_tiles ? nt + 4 : nt) : nt, last ? 0 : s + 1);
+            const RatB3 as[2] = {A.row_frag(mt0, s), A.row_frag(mt0 + 1, s)};
+            rat_mfma3_block<2>(acc, as, b);
+            b = bn;
+        }
+        epi(mt0, nt, acc[0]);
+        epi(mt0 + 1, nt, acc[1]);
+    }
+}
+
+// threadIdx.x as a value the compiler cannot see through: what a phase derives from it (row / piece / task indices, LDS addresses) is then
+// computed in that phase instead of being hoisted out of the chunk loop and carried through the GEMMs — hoisted, those values cost ~40 of
+// the 128 registers and some of them were spilled (a reload is a scratch load that waits for vmcnt(0))
+__device__ __forceinline__ int b3_tid_here() {
+    int t = threadIdx.x;
+#ifndef RAT_EMU
+    asm volatile("" : "+v"(t));
+#endif
+    return t;
+}
+
+template <bool EX>
+// (the second argument of hipcc's __launch_bounds__ counts WAVES PER SIMD, not work-groups per CU as in CUDA: 2 groups x 8 waves / 4 SIMDs)
+__global__ void __launch_bounds__(ATT_THREADS, 4) attn_fwd3_2wg_kernel(AttnArgs a, Attn3W W) {
+    RAT_DYN_SMEM(smem);
+    const PlanesX xp{smem};                                                 // R0: LayerNorm(x) planes ...
+    float* const qs = reinterpret_cast<float*>(smem);                       // ... fp32 Q [64][84]; O overwrites Q ...
+    float* const ys = reinterpret_cast<float*>(smem);                       // ... the projection's fp32 staging tile [64][68]
+    float* const kv = reinterpret_cast<float*>(smem + B3_F2_KV);            // R1: fp32 K|V [64][164] ...
+    const PlanesO op{smem + B3_F2_KV};                                      // ... O planes (row operand of the output projection)
+    int64_t* const rowtok0 = reinterpret_cast<int64_t*>(smem + B3_F2_MAP);
+    float* const lse_s = reinterpret_cast<float*>(smem + B3_F2_LSE);
+    float* const ln_s = reinterpret_cast<float*>(smem + B3_F2_LN);          // gamma [64] | beta [64]
+    constexpr int LDY = B3_D + 4;
+    const int L = a.L;
+    if ((int)threadIdx.x < 2 * B3_D) ln_s[threadIdx.x] = (int)threadIdx.x < B3_D ? a.ln_g[threadIdx.x] : a.ln_b[threadIdx.x - B3_D];
+    {
+        int nsq0, rows0;
+        map_rows(a, blockIdx.x, rowtok0, nsq0, rows0);
+    }
+    __syncthreads();
+    RAT_PROF_DECL
+    int parity = 0;
+    for (int64_t chunk = blockIdx.x; chunk < a.nchunks; chunk += gridDim.x, parity ^= 1) {
+        const int64_t* rowtok = rowtok0 + parity * ATT_ROWS;
+        int nsq, rows;
+        {
+            const int64_t q0 = chunk * a.nsq_chunk;
+            const int64_t left = a.nseq - q0;
+            nsq = left < a.nsq_chunk ? (int)left : a.nsq_chunk;
+            rows = nsq * a.L;
+        }
+        float4 x0, x1;                                           // kept: the residual of the plain PreNorm(Attention)(x) + x layer
+        b3_load_piece(a.x, rowtok, x0, x1);
+        {
+            float gam[8], bet[8];
+            const float4 g0 = *reinterpret_cast<const float4*>(ln_s + 8 * (threadIdx.x & 7)), g1 = *reinterpret_cast<const float4*>(ln_s + 8 * (threadIdx.x & 7) + 4);
+            const float4 b0 = *reinterpret_cast<const float4*>(ln_s + B3_D + 8 * (threadIdx.x & 7)), b1 = *reinterpret_cast<const float4*>(ln_s + B3_D + 8 * (threadIdx.x & 7) + 4);
+            gam[0] = g0.x; gam[1] = g0.y; gam[2] = g0.z; gam[3] = g0.w; gam[4] = g1.x; gam[5] = g1.y; gam[6] = g1.z; gam[7] = g1.w;
+            bet[0] = b0.x; bet[1] = b0.y; bet[2] = b0.z; bet[3] = b0.w; bet[4] = b1.x; bet[5] = b1.y; bet[6] = b1.z; bet[7] = b1.w;
+            b3_layer_norm_to_planes<false>(rowtok[threadIdx.x >> 3] >= 0, x0, x1, a.eps, xp, gam, bet, nullptr, nullptr);
+        }
+        if (chunk + gridDim.x < a.nchunks) {
+            int nsq1, rows1;
+            map_rows(a, chunk + gridDim.x, (rowtok0 + (parity ^ 1) * ATT_ROWS), nsq1, rows1);
+        }
+        __syncthreads();
+        RAT_PROF_MARK(0);
+        // Q|K|V = LN(x) W_qkv^T; Q over the x planes once every wave holds its A fragments
+        b3_gemm_rows_release<2>(xp, W.qkv, B3_Q3 / 16, [&](int mt, int nt, const f32x4& acc) {
+            const int col = rat_acc_col(nt);
+            float* const dst = nt < B3_I / 16 ? qs + col : kv + (col - B3_I);      // (wave-uniform)
+            const int ld = nt < B3_I / 16 ? B3_LDQ2 : B3_LDK2;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dst[(size_t)rat_acc_row(mt, r) * ld] = acc[r];
+        });
+        __syncthreads();
+        RAT_PROF_MARK(1);
+        // softmax(Q K^T * scale) V on the VALU: the loop of attn_fwd3_kernel on the two tiles
+        float pf = 0.f;
+        int tid = b3_tid_here();
+        if (tid < ATT_ROWS * 2 && chunk + gridDim.x < a.nchunks)
+            pf = prefetch_lines_map((rowtok0 + (parity ^ 1) * ATT_ROWS), tid, 2, a.x, B3_D);
+        typedef HeadVec<B3_DH> HV;
+        const int ntasks = nsq * B3_H * L;
+        const float sl2 = a.scale * RAT_LOG2E;
+        for (int task = tid; task < ntasks; task += ATT_THREADS) {
+            const int i = task % L;
+            const int h = (task / L) % B3_H;
+            const int sq = task / (L * B3_H);
+            const int row_i = sq * L + i;
+            float* qp = qs + (size_t)row_i * B3_LDQ2 + h * B3_DH;
+            HV q, o, kk1;
+            q.load(qp, B3_DH);
+            o.zero();
+            float m = -INFINITY, l = 0.f;
+            const float* kbase = kv + (size_t)(sq * L) * B3_LDK2 + h * B3_DH;
+            int j = 0;
+            for (; j + CORE_UNROLL <= L; j += CORE_UNROLL) {
+                HV kk[CORE_UNROLL], vv[CORE_UNROLL];
+#pragma unroll
+                for (int u = 0; u < CORE_UNROLL; ++u) {
+                    const float* kp = kbase + (size_t)(j + u) * B3_LDK2;
+                    kk[u].load(kp, B3_DH);
+                    vv[u].load(kp + B3_I, B3_DH);
+                }
+                float sc[CORE_UNROLL];
+#pragma unroll
+                for (int u = 0; u < CORE_UNROLL; ++u) sc[u] = q.dot(kk[u]) * sl2;
+#pragma unroll
+                for (int u = 0; u < CORE_UNROLL; ++u) {
+                    const float mn = fmaxf(m, sc[u]);
+                    const float corr = rat_exp2(m - mn);
+                    const float p = rat_exp2(sc[u] - mn);
+                    l = l * corr + p;
+                    o.scale_axpy(corr, p, vv[u]);
+                    m = mn;
+                }
+            }
+            for (; j < L; ++j) {
+                const float* kp = kbase + (size_t)j * B3_LDK2;
+                kk1.load(kp, B3_DH);
+                const float sv = q.dot(kk1) * sl2;
+                const float mn = fmaxf(m, sv);
+                const float corr = rat_exp2(m - mn);
+                const float p = rat_exp2(sv - mn);
+                l = l * corr + p;
+                kk1.load(kp + B3_I, B3_DH);
+                o.scale_axpy(corr, p, kk1);
+                m = mn;
+            }
+            const float inv = 1.0f / l;
+            o.store(qp, B3_DH, inv);
+            lse_s[row_i * B3_H + h] = m + rat_log2(l);
+        }
+        __syncthreads();
+        RAT_PROF_MARK(2);
+        // O (R0; padding rows are exact zeros) -> planes over the dead K|V tile, and -> o_save / lse_save as whole rows
+        tid = b3_tid_here();
+        if (tid < 3 * 16)                                        // the planes' slack: 64 bytes behind each plane's 64 rows
+            *reinterpret_cast<float*>(op.base + (size_t)(tid >> 4) * B3_OP + 64 * 160 + 4 * (tid & 15)) = 0.f;
+        for (int e = tid; e < ATT_ROWS * (B3_I / 8); e += ATT_THREADS) {
+            const int r = e / (B3_I / 8), o8 = e - r * (B3_I / 8);
+            const float* src = qs + (size_t)r * B3_LDQ2 + 8 * o8;
+            const float4 v0 = *reinterpret_cast<const float4*>(src), v1 = *reinterpret_cast<const float4*>(src + 4);
+            rat_u4 h, m, l;
+            rat_split8(v0, v1, h, m, l);
+            op.store(r, o8, h, m, l);
+            const int64_t tok = rowtok[r];
+            if (a.o_save != nullptr && tok >= 0) {
+                rat_st4_stream(a.o_save + tok * B3_I + 8 * o8, v0);
+                rat_st4_stream(a.o_save + tok * B3_I + 8 * o8 + 4, v1);
+            }
+        }
+        if (a.lse_save != nullptr && tid < (B3_H / 4) * ATT_ROWS) {
+            const int r = tid / (B3_H / 4), part = tid % (B3_H / 4);
+            const int64_t tok = rowtok[r];
+            if (tok >= 0) rat_st4_stream(a.lse_save + tok * B3_H + 4 * part, *reinterpret_cast<const float4*>(lse_s + r * B3_H + 4 * part));
+        }
+        __syncthreads();
+        RAT_PROF_MARK(3);
+        // y = O W_out^T + b_out (+ residual), staged through LDS (over the fp32 O, read for the last time before the barrier above)
+        b3_gemm_rows_stream<3>(op, W.out, B3_D / 16, [&](int mt, int nt, const f32x4& acc) {
+            const int col = rat_acc_col(nt);
+            const float bias = a.b_out[col];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ys[(size_t)rat_acc_row(mt, r) * LDY + col] = acc[r] + bias;
+        });
+        __syncthreads();
+        RAT_PROF_MARK(4);
+        if (EX) {
+            store_rows_residual(a.y, ys, LDY, a.res, rowtok, rows, B3_D, true, a.out_scale, &a.drop);
+        } else {                                                 // y = tile + x, the x piece still in registers: no global re-read
+            tid = b3_tid_here();
+            const int r = tid >> 3, sb = tid & 7;
+            const int64_t tok = rowtok[r];
+            if (tok >= 0) {
+                const float4 t0 = *reinterpret_cast<const float4*>(ys + (size_t)r * LDY + 8 * sb);
+                const float4 t1 = *reinterpret_cast<const float4*>(ys + (size_t)r * LDY + 8 * sb + 4);
+                *reinterpret_cast<float4*>(a.y + tok * B3_D + 8 * sb) = make_float4(t0.x + x0.x, t0.y + x0.y, t0.z + x0.z, t0.w + x0.w);
+                *reinterpret_cast<float4*>(a.y + tok * B3_D + 8 * sb + 4) = make_float4(t1.x + x1.x, t1.y + x1.y, t1.z + x1.z, t1.w + x1.w);
             }
         }
         __syncthreads();

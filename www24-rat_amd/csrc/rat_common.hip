@@ -31,19 +31,25 @@ int rat_check_launch(const char* what) {
 //   attn_bwd_core_mfma (RAT_ATTN_BWD_CORE=mfma|valu) 1 / 0: force the matrix-pipe / VALU backward core whatever L says (-1: by L)
 //   ffn_bwd_t3 (RAT_FFN_BWD=t3)                1: round 3's feed-forward backward kernel
 //   sgemm_split_target (RAT_SGEMM_SPLIT_TARGET=<n>)  work-groups the split-K rule of the head's GEMMs aims for (0: built-in)
+//   attn_fwd_2wg (RAT_ATTN_FWD_2WG=0|1)        1 / 0: force attn_fwd3_2wg_kernel (69 KB of LDS, 128 VGPRs: two work-groups per CU) on for every shape
+//                                              it covers (embedding_dim 64, 8 heads x 10, VALU core, every position a query) / off: attn_fwd3_kernel's
+//                                              one-group form.  -1 (default): on wherever it is covered (no rule by length yet).  Both forms give bit-identical
+//                                              y / o_save / lse_save.  Per launch -11 % (L = 21) / -12 % (L = 11), the eval forward -9.4 %, the
+//                                              north-star step -1.7 % (profiles/attn_fwd_2wg/ab.txt; b3_fwd_two_groups in attn.hip).
 static int g_knobs[RAT_KNOB_COUNT];
 static const char* const g_knob_names[RAT_KNOB_COUNT] = {"max_blocks", "attn_bwd_ph", "attn_fwd_core_mfma", "attn_bwd_core_mfma", "ffn_bwd_t3",
-                                                         "sgemm_split_target"};
+                                                         "sgemm_split_target", "attn_fwd_2wg"};
 static const bool g_knobs_loaded = [] {
     auto env = [](const char* n) { const char* e = getenv(n); return e ? std::string(e) : std::string(); };
     const std::string mb = env("RAT_MAX_BLOCKS"), ph = env("RAT_ATTN_BWD_PH"), fc = env("RAT_ATTN_FWD_CORE"), bc = env("RAT_ATTN_BWD_CORE"),
-                      ff = env("RAT_FFN_BWD"), st = env("RAT_SGEMM_SPLIT_TARGET");
+                      ff = env("RAT_FFN_BWD"), st = env("RAT_SGEMM_SPLIT_TARGET"), f2 = env("RAT_ATTN_FWD_2WG");
     g_knobs[RAT_KNOB_MAX_BLOCKS] = mb.empty() ? 0 : atoi(mb.c_str());
     g_knobs[RAT_KNOB_ATTN_BWD_PH] = (ph.empty() || ph[0] != '0') ? 1 : 0;
     g_knobs[RAT_KNOB_ATTN_FWD_CORE_MFMA] = fc == "mfma" ? 1 : (fc == "mfma32" ? 2 : (fc == "valu" ? 3 : 0));
     g_knobs[RAT_KNOB_ATTN_BWD_CORE_MFMA] = bc == "mfma" ? 1 : (bc == "valu" ? 0 : -1);
     g_knobs[RAT_KNOB_FFN_BWD_T3] = ff.rfind("t3", 0) == 0 ? 1 : 0;
     g_knobs[RAT_KNOB_SGEMM_SPLIT_TARGET] = st.empty() ? 0 : (atoi(st.c_str()) > 0 ? atoi(st.c_str()) : 0);
+    g_knobs[RAT_KNOB_ATTN_FWD_2WG] = f2.empty() ? -1 : (f2[0] == '0' ? 0 : 1);
     return true;
 }();
 int rat_knob(int which) { return g_knobs[which]; }
