@@ -407,6 +407,23 @@ int rat_batch_assemble_ring(const int32_t* data_ids, const float* data_labels, c
                             const int64_t* retr_indices, const int64_t* rows, int32_t* idx, int32_t* label_ids, float* y_true,
                             int64_t Q, const int64_t* header_dev, int64_t capacity, int B, int K, int L, void* stream);
 
+/* A pool that loses rows (additive in ABI v9 as well): arbitrary rows leave the ring above, the survivors close up IN PLACE and in age
+ * order, so that the scan, the merge and the assembly serve the result unchanged.
+ *
+ * rat_pool_delete: del_dev [n_del] int64 (device) are LOGICAL indices, strictly ascending (the caller sorts and validates them).  Live
+ * row j that is not listed ends at logical position j - #{listed rows < j} in all three stores (slot head + position, wrapped); rows
+ * older than del_dev[0] are not touched, head does not move, and a one-thread tail launch sets n = n - n_del.  The move is staged through
+ * `scratch`, one store after the other in stream order: a launch gathers the survivors of the suffix [del_dev[0], n) in compact order
+ * (64 consecutive rows of a column per wave for db_ids_field_major, words for pool_ids, as rat_pool_push addresses them), the next one
+ * copies them back — no work-group waits for another.  scratch_bytes >= 4 capacity max(n_fields, row_len) (4 capacity n_fields when
+ * pool_ids and pool_labels are NULL — they go together, as for rat_pool_push), 4-byte aligned; it is not read between calls.  All
+ * launches read the header on the device: a delete queues behind pushes and evictions without a synchronisation, and the grid depends
+ * on the capacity only.  n_del <= 0 launches nothing.  n_del >= n (the pool would become empty) moves nothing and leaves the header.
+ * For ANY header or list content nothing outside the buffers is addressed (n is clamped to [0, capacity], head to [0, capacity),
+ * del_dev[0] to [0, n]; a source row is always a live one); what the stores then hold is unspecified. */
+int rat_pool_delete(int32_t* db_ids_field_major, int32_t* pool_ids, float* pool_labels, int64_t* header_dev, const int64_t* del_dev,
+                    void* scratch, size_t scratch_bytes, int64_t n_del, int64_t capacity, int row_len, int n_fields, void* stream);
+
 /* ---- K3: prediction head -----------------------------------------------------------------------------
  * Plain fp32 GEMM on MFMA for MLP_Layer's nn.Linear (deep.py:126-141) forward / dgrad / wgrad:
  * C[M][N] = op(A) op(B) (+ bias[N]) (+ beta*C), row-major with leading dimensions, op = transpose flag. */

@@ -19,6 +19,12 @@ alternating round by round in one process, at least 0.5 s of timed work per poin
 scorer with capacity and window=True against the capacity-mode scorer over the same rows, at B in {1, 16, 256}, once with the ring's
 head at 0 and once after enough pushes that the live rows wrap through the end of the buffer; (ii) append(M) on a FULL window (the M
 oldest rows leave) against a new RetrievalIndex over the shifted pool, for M in {1, 64, 4096}.
+--delete — deletion from the sliding pool instead (profiles/online/delete_bench.txt), same geometry, clock and alternation:
+(i) RetrievalIndex.delete(m seeded random rows) on a window=True index against what an index without it makes a user do — a new
+RetrievalIndex over np.delete(pool, rows) — for m in {1, 64, 4096}, with the ring's head at 0 and wrapped (the deleted rows are
+appended again between rounds, untimed, so every round sees the same row count); (iii) replayed score() of one scorer at B in
+{1, 16, 256} immediately after a deletion of 4096 rows against immediately before it.  --delete --trace runs the deletions of (i)
+alone, a few per point, for a kernel trace taken in a run of its own: (ii), the device time of the delete launches.
 There is no CPU fallback: without a GPU the tool exits with an error."""
 import argparse
 import os
@@ -250,17 +256,22 @@ def part_append(emit, quick):
         emit("B %4d | capacity %s | immutable %s | capacity / immutable = %.4f" % (B, _stats(per["capacity"]), _stats(per["immutable"]), a / b))
 
 
+def _replay_round(sc, ids, rounds_of=200):
+    """us per request over one round of `rounds_of` requests, each followed by a synchronise"""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(rounds_of):
+        sc.score(ids)
+        torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / rounds_of * 1e6
+
+
 def _replay_rounds(sides, ids, min_s, rounds_of=200):
     """sides: {label: scorer with the request captured} -> {label: [us per request of every round]}, the sides alternating"""
     per = {k: [] for k in sides}
     while min(sum(v) for v in per.values()) * rounds_of / 1e6 < min_s:
         for label, sc in sides.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(rounds_of):
-                sc.score(ids)
-                torch.cuda.synchronize()
-            per[label].append((time.perf_counter() - t0) / rounds_of * 1e6)
+            per[label].append(_replay_round(sc, ids, rounds_of))
     return per
 
 
@@ -338,12 +349,115 @@ def part_window(emit, quick):
     emit("   (afterwards retrieve() equals a fresh index over the live rows, bit for bit; head = %d)" % index.count.cpu().tolist()[1])
 
 
+def _wrap(obj, rows, cur, n_pool, capacity):
+    """obj holds the n_pool rows `cur` from slot 0 on: push until half of the live rows lie before the wrap, then evict back to n_pool
+    rows -> the live rows, oldest first"""
+    push = capacity - n_pool + n_pool // 2
+    while push > 0:
+        new = rows(min(push, 200_000))
+        obj.append(new)
+        cur = np.concatenate([cur, new])[-capacity:]
+        push -= len(new)
+    obj.evict(capacity - n_pool)
+    return cur[capacity - n_pool:]
+
+
+def part_delete(emit, quick, trace):
+    from rat_amd.online import OnlineScorer, RetrievalIndex
+    name, model, rows, vocab, cfg, n_pool, capacity = _movielens(quick)
+    dev, K, cols = torch.device("cuda:0"), cfg["topK"], cfg["used_col_indices"]
+    min_ms = 50.0 if quick else MIN_TIMED_MS                               # of timed work per point and side
+    min_s = min_ms / 1e3
+    pool = rows(n_pool)
+    rs = np.random.RandomState(5)
+    requests = {B: torch.from_numpy(np.stack([rs.randint(0, v, size=B) for v in vocab], axis=1).astype(np.int32)).to(dev)
+                for B in (1, 16, 256)}
+    emit("== delete (i): m seeded random rows leave a window of %d live rows (%d columns) in a capacity of %d [ms per call]: "
+         "RetrievalIndex.delete against a new RetrievalIndex over np.delete(pool, rows) (np.delete included); host clock + synchronise, "
+         "alternating; the deleted rows are appended again between rounds, untimed" % (n_pool, len(cols), capacity))
+    index = RetrievalIndex(pool, cols, K, dev, capacity=capacity, window=True)
+    cur = pool
+    for state in ("head = 0", "wrapped"):
+        if state == "wrapped":
+            cur = _wrap(index, rows, cur, n_pool, capacity)
+            n, head = index.count.cpu().tolist()
+            assert n == n_pool and head + n > capacity, (n, head)
+            emit("   after the pushes: n = %d, head = %d — %d live rows before the wrap, %d after it" % (n, head, capacity - head,
+                                                                                                      n - (capacity - head)))
+        for m in (1, 64, 4096):
+            t_del, t_new = [], []
+            while len(t_del) < 5 if trace else (sum(t_del) < min_ms or len(t_del) < 3 or sum(t_new) < min_ms or len(t_new) < 3):
+                idx = rs.choice(len(index), m, replace=False)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                index.delete(idx)
+                torch.cuda.synchronize()
+                t_del.append((time.perf_counter() - t0) * 1e3)
+                if not trace and (sum(t_new) < min_ms or len(t_new) < 3):    # the same rows out of the same pool, the immutable way
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fresh = RetrievalIndex(np.delete(cur, idx, axis=0), cols, K, dev)
+                    torch.cuda.synchronize()
+                    t_new.append((time.perf_counter() - t0) * 1e3)
+                    del fresh
+                new = rows(m)
+                index.append(new)                              # back to n_pool rows: there is room, nobody leaves
+                cur = np.concatenate([np.delete(cur, idx, axis=0), new])
+            if trace:
+                emit("%-8s m %5d | delete %s" % (state, m, _stats(t_del)))
+                continue
+            a, b = sum(t_del) / len(t_del), sum(t_new) / len(t_new)
+            emit("%-8s m %5d | delete %s | new index %s | delete / new index = %.5f (%.1fx)" % (state, m, _stats(t_del), _stats(t_new),
+                                                                                                a / b, b / a))
+    fresh = RetrievalIndex(cur, cols, K, dev)
+    for g, w in zip(index.retrieve(requests[16]), fresh.retrieve(requests[16])):
+        assert torch.equal(g.view(torch.int64), w.view(torch.int64)), "index after deletions != fresh index"
+    emit("   (afterwards retrieve() equals a fresh index over the live rows, bit for bit; n, head = %s)" % index.count.cpu().tolist())
+    del index, fresh
+    if trace:
+        return
+
+    m = 4096
+    emit("== delete (iii): replayed OnlineScorer.score() [us per request], %s, window=True, %d live rows in a capacity of %d: immediately "
+         "after delete(%d random rows) against immediately before it, the same scorer and the same captured request; host clock + "
+         "synchronise, rounds of 200 requests, before and after alternating (the rows are appended again after every round)"
+         % (name, n_pool, capacity, m))
+    scorer = OnlineScorer(model, pool, cfg, graph=True, capacity=capacity, window=True)
+    cur = pool
+    for B, ids in requests.items():
+        for _ in range(5):
+            scorer.score(ids)
+        torch.cuda.synchronize()
+    assert all(e[1] for e in scorer._graphs.values()) and len(scorer._graphs) == 3, "the requests were not captured"
+    for B, ids in requests.items():
+        per = {"before": [], "after": []}
+        while min(sum(v) for v in per.values()) * 200 / 1e6 < min_s:
+            per["before"].append(_replay_round(scorer, ids))
+            idx = rs.choice(len(scorer.index), m, replace=False)
+            scorer.delete(idx)
+            per["after"].append(_replay_round(scorer, ids))
+            new = rows(m)
+            scorer.append(new)
+            cur = np.concatenate([np.delete(cur, idx, axis=0), new])
+        a, b = (sum(per[k]) / len(per[k]) for k in ("after", "before"))
+        emit("B %4d | after %s | before %s | after / before = %.4f" % (B, _stats(per["after"]), _stats(per["before"]), a / b))
+    assert len(scorer._graphs) == 3 and all(e[1] for e in scorer._graphs.values()), "a deletion invalidated a captured request"
+    idx = rs.choice(len(scorer.index), m, replace=False)
+    scorer.delete(idx)
+    fresh = OnlineScorer(model, np.delete(cur, idx, axis=0), cfg, graph=False)
+    assert torch.equal(scorer.score(requests[16]), fresh.score(requests[16])), "replay after a deletion != fresh scorer"
+    emit("   (the replayed request after the last deletion equals a fresh scorer over the remaining rows, bit for bit; %d graphs kept)"
+         % len(scorer._graphs))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the report to this file")
     ap.add_argument("--quick", action="store_true", help="a few small points only (plumbing check)")
     ap.add_argument("--append", action="store_true", help="measure the growing pool (append against a new index; replay with capacity)")
     ap.add_argument("--window", action="store_true", help="measure the sliding pool (replay with window=True; append on a full window)")
+    ap.add_argument("--delete", action="store_true", help="measure deletion from the sliding pool (delete against a new index; replay)")
+    ap.add_argument("--trace", action="store_true", help="with --delete: only a few deletions per point, for a kernel trace")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("online_bench.py measures on the GPU; no GPU is visible and there is no CPU fallback")
@@ -362,6 +476,9 @@ def main():
         return
     if args.window:
         part_window(emit, args.quick)
+        return
+    if args.delete:
+        part_delete(emit, args.quick, args.trace)
         return
     part1(emit, args.quick)
     part2(emit, args.quick)

@@ -629,3 +629,134 @@ extern "C" int rat_pool_evict(int64_t* header_dev, int64_t n_rows, int64_t capac
     RAT_LAUNCH(pool_evict_kernel, 1u, 64, 0, stream, header_dev, n_rows, capacity);
     return rat_check_launch("rat_pool_evict");
 }
+
+// ------------------------------------------------------------------------------------------------------------ a pool that loses rows
+// rat_pool_delete: the rows named by a strictly ascending list of logical indices leave the ring, the survivors close up in age order.
+// Survivor j ends at logical j - #{deleted < j}: a destination is at or before its source and the ranges overlap, so the move is
+// staged — per store ("plane"), launch 1 gathers the survivors of the suffix [del[0], n) into scratch in compact order, launch 2
+// copies them back from logical del[0] on; stream order is the only ordering between work-groups.  Both are destination-driven:
+// compact position j' takes logical row j' + k, k = the number of list entries with del[k] - k <= j' (that sequence is
+// non-decreasing: a binary search).  Rows older than del[0] are not touched, head does not move, the tail launch sets n -= n_del.
+namespace {
+
+struct DeleteArgs {
+    int32_t* db_t;           // [F][capacity]
+    int32_t* pool_ids;       // [capacity][L]   (nullable, with pool_labels)
+    float* pool_labels;      // [capacity]
+    const int64_t* header;   // {n, head}
+    const int64_t* del;      // [n_del] logical indices, strictly ascending
+    int32_t* scratch;        // capacity * max(F, L) words (capacity * F without the row store)
+    int64_t n_del, capacity;
+    int L, F;
+};
+
+enum { PLANE_DB_T = 0, PLANE_IDS = 1, PLANE_LABELS = 2 };
+constexpr int64_t DEL_ITEMS_PER_THREAD = 4;            // the grid is sized for this many words per thread at the full capacity
+
+// What both launches of a plane see.  n is clamped to [0, capacity], head to [0, capacity) and del[0] to [0, n], as the ring scan
+// clamps its header: compact positions are [first, n - n_del) and a source is j' + k <= n - n_del - 1 + n_del, a live row whatever
+// the list holds — nothing outside the buffers is addressed for any header or list content.
+struct DeleteView {
+    int64_t n, head, first, count;                     // count = survivors of the suffix = compact positions to move
+};
+__device__ __forceinline__ DeleteView delete_view(const DeleteArgs& a) {
+    DeleteView v;
+    v.n = a.header[0];
+    v.n = v.n < 0 ? 0 : (v.n > a.capacity ? a.capacity : v.n);
+    v.head = a.header[1];
+    v.head = v.head < 0 ? 0 : (v.head >= a.capacity ? a.capacity - 1 : v.head);
+    v.first = a.del[0];
+    v.first = v.first < 0 ? 0 : (v.first > v.n ? v.n : v.first);
+    v.count = v.n - a.n_del - v.first;
+    v.count = v.count < 0 ? 0 : v.count;
+    return v;
+}
+// number of list entries k with del[k] - k <= j
+__device__ __forceinline__ int64_t deleted_up_to(const int64_t* del, int64_t n_del, int64_t j) {
+    int64_t lo = 0, hi = n_del;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (del[mid] - mid <= j)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// Work items e of a plane, as pool_push_kernel addresses the stores: db_t — e = f * count + i, 64 consecutive lanes move 64
+// consecutive rows of one column (in two pieces where the wrap falls among them); pool_ids — word e = i * L + c of the compact rows;
+// labels — e = i.  BACK = false: scratch[e] = store[slot of logical first + i + k]; BACK = true: store[slot of logical first + i] =
+// scratch[e].
+template <int PLANE, bool BACK>
+__global__ void __launch_bounds__(256) pool_delete_move_kernel(DeleteArgs a) {
+    const DeleteView v = delete_view(a);
+    const int64_t width = PLANE == PLANE_DB_T ? a.F : (PLANE == PLANE_IDS ? a.L : 1);
+    const int64_t total = v.count * width;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t i = PLANE == PLANE_DB_T ? e % v.count : (PLANE == PLANE_IDS ? e / a.L : e);
+        const int64_t w = PLANE == PLANE_DB_T ? e / v.count : (PLANE == PLANE_IDS ? e % a.L : 0);      // column f / word c of the row
+        int64_t row = v.first + i;
+        if constexpr (!BACK) row += deleted_up_to(a.del, a.n_del, row);
+        const int64_t slot = ring_wrap(v.head + row, a.capacity);
+        if constexpr (PLANE == PLANE_LABELS) {
+            float* lab = reinterpret_cast<float*>(a.scratch);
+            if constexpr (BACK)
+                a.pool_labels[slot] = lab[e];
+            else
+                lab[e] = a.pool_labels[slot];
+        } else {
+            int32_t* at = PLANE == PLANE_DB_T ? a.db_t + w * a.capacity + slot : a.pool_ids + slot * a.L + w;
+            if constexpr (BACK)
+                *at = a.scratch[e];
+            else
+                a.scratch[e] = *at;
+        }
+    }
+}
+
+// the tail launch: the survivors are in place (stream order), now the deleted rows stop counting; the pool never becomes empty
+__global__ void __launch_bounds__(64) pool_delete_commit_kernel(int64_t* header, int64_t n_del, int64_t capacity) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        const RingHeader h = ring_header(header, capacity);
+        if (!h.ok || n_del <= 0 || n_del >= h.n) return;
+        header[0] = h.n - n_del;
+    }
+}
+
+template <int PLANE>
+int launch_delete_plane(const DeleteArgs& a, int64_t width, void* stream) {
+    const int64_t per_block = 256 * DEL_ITEMS_PER_THREAD;
+    const int64_t blocks = (a.capacity * width + per_block - 1) / per_block;
+    const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
+    RAT_LAUNCH((pool_delete_move_kernel<PLANE, false>), grid, 256, 0, stream, a);
+    if (rat_check_launch("rat_pool_delete") != 0) return -1;
+    RAT_LAUNCH((pool_delete_move_kernel<PLANE, true>), grid, 256, 0, stream, a);
+    return rat_check_launch("rat_pool_delete");
+}
+
+}  // namespace
+
+extern "C" int rat_pool_delete(int32_t* db_ids_field_major, int32_t* pool_ids, float* pool_labels, int64_t* header_dev,
+                               const int64_t* del_dev, void* scratch, size_t scratch_bytes, int64_t n_del, int64_t capacity, int row_len,
+                               int n_fields, void* stream) {
+    RAT_REQUIRE(db_ids_field_major && header_dev, "null pointer");
+    RAT_REQUIRE((pool_ids == nullptr) == (pool_labels == nullptr), "pool_ids and pool_labels go together");
+    RAT_REQUIRE(capacity > 0 && row_len > 0 && n_fields > 0, "bad dims");
+    RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
+    if (n_del <= 0) return 0;                          // nothing to delete: nothing is launched
+    RAT_REQUIRE(del_dev && scratch, "null pointer");
+    RAT_REQUIRE(n_del <= capacity, "more deletions than the window holds rows");
+    const int64_t width = pool_ids && row_len > n_fields ? row_len : n_fields;
+    RAT_REQUIRE(scratch_bytes / sizeof(int32_t) / (size_t)capacity >= (size_t)width, "scratch smaller than the largest store");
+    RAT_REQUIRE(((uintptr_t)scratch & 3) == 0, "scratch must be 4-byte aligned");
+    DeleteArgs a{db_ids_field_major, pool_ids, pool_labels, header_dev, del_dev, static_cast<int32_t*>(scratch), n_del, capacity,
+                 row_len, n_fields};
+    if (launch_delete_plane<PLANE_DB_T>(a, n_fields, stream) != 0) return -1;
+    if (pool_ids) {
+        if (launch_delete_plane<PLANE_IDS>(a, row_len, stream) != 0) return -1;
+        if (launch_delete_plane<PLANE_LABELS>(a, 1, stream) != 0) return -1;
+    }
+    RAT_LAUNCH(pool_delete_commit_kernel, 1u, 64, 0, stream, header_dev, n_del, capacity);
+    return rat_check_launch("rat_pool_delete");
+}

@@ -164,6 +164,8 @@ _SIGNATURES = {
     "rat_pool_evict": (c_int, [_P, c_int64, c_int64, _P]),
     "rat_bm25_topk_split_ring": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_size_t, c_int64, c_int64, c_int, c_int, c_int, _P]),
     "rat_batch_assemble_ring": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_int, c_int, c_int, _P]),
+    # a pool that loses rows: the survivors of a ring close up in place, staged through a scratch buffer
+    "rat_pool_delete": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t, c_int64, c_int64, c_int, c_int, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

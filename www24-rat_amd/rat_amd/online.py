@@ -30,9 +30,15 @@ alike, and at any moment the object answers exactly like a fresh one over the li
 of the live rows in a host ring to know which ids leave; an id whose count reaches zero leaves its column's table.
 Without ``window`` a pool with ``capacity`` is append-only and refuses rows when it is full.
 
+The window can lose any row.  ``delete(indices)`` (``window=True`` only) takes logical positions as ``retrieve`` returns them; the
+survivors close up in place and in age order on the device (``rat_pool_delete``, staged through a scratch buffer the index allocates
+on the first delete), every survivor's index drops by the number of deleted rows older than it, and ``head`` stays.  The host ring is
+compacted the same way and the counts of the deleted rows leave the tables, so afterwards the object again answers exactly like a fresh
+one over the live rows in age order — and captured request graphs are kept, as the row count is read on the device.
+
 Not served online (refused at construction): exact-match columns (numbering the groups needs a host ``np.unique`` over pool and
-queries), label-wise retrieval, topK > 32, more than 32 retrieval columns, data-parallel models.  Rows leave oldest first only: there
-is no deletion of an arbitrary row (a pool that loses other rows is a new ``RetrievalIndex``).
+queries), label-wise retrieval, topK > 32, more than 32 retrieval columns, data-parallel models.  Rows are deleted from a
+``window=True`` pool only: the append-only form reserves its IDF tables for the rows that can still come, which deletions would undo.
 """
 import numpy as np
 import torch
@@ -84,7 +90,10 @@ class RetrievalIndex:
     ``window=True`` (needs ``capacity``): the buffers are a ring over the most recent rows.  ``append`` evicts the oldest rows when
     they do not fit, ``evict(m)`` drops the m oldest; the index then equals a fresh one over the live rows, oldest first.  Memory:
     ``db_t`` is 4 F capacity bytes as before; a column can hold up to capacity distinct ids at some time, so every column's IDF table
-    is reserved in full — 12 F capacity bytes, three times ``db_t`` — and the host keeps 8 F capacity bytes of the live rows' ids."""
+    is reserved in full — 12 F capacity bytes, three times ``db_t`` — and the host keeps 8 F capacity bytes of the live rows' ids.
+    ``delete(indices)`` drops arbitrary live rows of a window; the index then equals a fresh one over the survivors, oldest first.
+    Its first call allocates a scratch buffer the size of the largest store it moves, kept from then on: 4 F capacity bytes, or
+    4 max(F, L) capacity bytes with an ``OnlineScorer``'s row store (L ids per row).  An index that never deletes does not pay for it."""
 
     def __init__(self, pool_array, col_indices, topK, device, lib=None, exact_match_col_indices=None, splits=0, capacity=None,
                  window=False):
@@ -126,7 +135,7 @@ class RetrievalIndex:
     def retrieve(self, ids):
         """ids [B, L] (full encoded rows) -> (values fp64 [B, K], indices int64 [B, K] with -1 padding, lens int64 [B]), on the device.
         With ``window=True`` the indices are LOGICAL positions (0 = the oldest live row, len(index) - 1 = the newest): they hold until
-        the next eviction (an ``evict``, or an ``append`` into a full window), which renumbers the rows."""
+        the next eviction (an ``evict``, or an ``append`` into a full window) or ``delete``, which renumber the rows."""
         ids = _as_device_ids(ids, self.device)
         if ids.shape[1] != self.row_len:
             raise ValueError("ids have %d columns, the pool's rows have %d" % (ids.shape[1], self.row_len))
@@ -160,6 +169,7 @@ class RetrievalIndex:
             self._ring = np.zeros((capacity, F), dtype=db.dtype)               # used columns of the live rows, slot-major: who leaves
             self._ring[:n] = db
             self._head = 0
+            self._scratch = None                                               # rat_pool_delete's staging buffer, from the first delete on
         self.table_ids = torch.zeros(table_cap, dtype=torch.int32, device=dev)
         self.table_idf = torch.zeros(table_cap, dtype=torch.float64, device=dev)
         self.table_offsets = torch.zeros(F + 1, dtype=torch.int64, device=dev)
@@ -214,10 +224,15 @@ class RetrievalIndex:
         return (self._head + first + np.arange(m)) % self.capacity
 
     def _count_out(self, m):
-        """the m oldest rows leave the mirrored counts; an id nobody holds any more leaves its column's table, as a fresh index over
-        the remaining rows would not hold it (a request whose first row carries it then MISSES: the dtype rule of
-        rat_bm25_query_prepare depends on that)"""
-        gone = self._ring[self._slots(0, m)]
+        """the m oldest rows leave the mirrored counts and the host ring"""
+        self._count_gone(self._ring[self._slots(0, m)])
+        self._head = (self._head + m) % self.capacity
+        self.n_db -= m
+
+    def _count_gone(self, gone):
+        """gone [m, F] (the used columns of rows going out) leave the mirrored counts; an id nobody holds any more leaves its column's
+        table, as a fresh index over the remaining rows would not hold it (a request whose first row carries it then MISSES: the
+        dtype rule of rat_bm25_query_prepare depends on that)"""
         for f in range(gone.shape[1]):
             vals, counts = self._counts[f]
             u, uc = np.unique(gone[:, f], return_counts=True)
@@ -225,8 +240,6 @@ class RetrievalIndex:
             counts[np.searchsorted(vals, u)] -= uc
             keep = counts > 0
             self._counts[f] = (vals[keep], counts[keep])
-        self._head = (self._head + m) % self.capacity
-        self.n_db -= m
 
     def _push(self, ids32, as_int, labels, pool_ids, pool_labels):
         M = len(ids32)
@@ -260,6 +273,54 @@ class RetrievalIndex:
         ops.pool_evict(self.count, m, self.capacity, lib=self._lib)
         self._upload_tables()
 
+    def _delete_list(self, indices):
+        """what ``delete`` accepts -> sorted int64 [m] on the host, or ValueError"""
+        if torch.is_tensor(indices):
+            indices = indices.detach().cpu().numpy()
+        idx = np.atleast_1d(np.asarray(indices))
+        if idx.ndim != 1:
+            raise ValueError("delete takes a 1-D list of logical row indices, got shape %s" % (tuple(idx.shape),))
+        if idx.size == 0:
+            return np.zeros(0, dtype=np.int64)
+        if not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError("delete takes integer row indices, got dtype %s" % idx.dtype)
+        if idx.min() < 0 or idx.max() >= self.n_db:
+            raise ValueError("delete: index outside [0, %d), the live rows of the window (a negative index does not count from the end)"
+                             % self.n_db)
+        idx = np.sort(idx.astype(np.int64))
+        if (np.diff(idx) == 0).any():
+            raise ValueError("delete: duplicate index %d" % idx[1:][np.diff(idx) == 0][0])
+        if len(idx) >= self.n_db:
+            raise ValueError("delete of all %d rows would leave the pool empty (the window never becomes empty)" % self.n_db)
+        return idx
+
+    def delete(self, indices, _pool_ids=None, _pool_labels=None):
+        """The live rows at the logical positions ``indices`` (as ``retrieve`` returns them: an int array-like, a host or a device
+        tensor, in any order) leave the window (``window=True`` only).  The survivors keep their age order: every survivor's index
+        drops by the number of deleted rows older than it, every IDF weight moves (N and the counts) and ids nobody holds any more
+        leave the tables.  Ordered with the requests on the current stream; an empty list does nothing.  ValueError — and nothing
+        written — for a duplicate, an index outside [0, len(index)) (negative ones included), a non-integer dtype, a list that would
+        leave the pool empty."""
+        if not self.window:
+            raise ValueError("this index was built without window=True: rows cannot be deleted")
+        idx = self._delete_list(indices)
+        m, n = len(idx), self.n_db
+        if m == 0:
+            return
+        # what can fail comes first — the allocation, the upload of the list, the launches: the host state changes after them
+        words = self.capacity * max(len(self._col_list), self.row_len if _pool_ids is not None else 0)
+        if self._scratch is None or self._scratch.numel() < words:                 # outside every captured graph: no request reads it
+            self._scratch = torch.empty(words, dtype=torch.int32, device=self.device)
+        ops.pool_delete(self.db_t, self.count, torch.from_numpy(idx).to(self.device), self._scratch, _pool_ids, _pool_labels,
+                        lib=self._lib)
+        self._count_gone(self._ring[(self._head + idx) % self.capacity])
+        suffix = np.arange(idx[0], n)                                          # rows older than the first deleted one stay where they are
+        keep = np.ones(len(suffix), dtype=bool)
+        keep[idx - idx[0]] = False
+        self._ring[self._slots(idx[0], n - m - idx[0])] = self._ring[(self._head + suffix[keep]) % self.capacity]
+        self.n_db -= m
+        self._upload_tables()
+
 
 class _RequestGraph:
     """retrieve -> assemble -> eval forward of one request size as one linear hipGraph (one stream, no parallel branches)"""
@@ -286,8 +347,8 @@ class OnlineScorer:
     chain is captured and replayed; the weights are read at replay time, so the graph survives optimizer steps and load_state_dict.
     ``capacity``: room for that many pool rows; ``append(rows)`` then adds labelled rows in place and the captured graphs stay valid
     (they read the row count from device memory).  Append-only, unless ``window=True``: the pool is then a sliding window over the most
-    recent ``capacity`` rows — ``append`` evicts the oldest rows when the new ones do not fit, ``evict(m)`` drops the m oldest, and the
-    captured graphs stay valid through both."""
+    recent ``capacity`` rows — ``append`` evicts the oldest rows when the new ones do not fit, ``evict(m)`` drops the m oldest,
+    ``delete(indices)`` drops arbitrary rows, and the captured graphs stay valid through all three."""
 
     graph_warmup = 2
     graph_max_batch = 4096
@@ -354,6 +415,12 @@ class OnlineScorer:
         """``RetrievalIndex.evict``: the m oldest pool rows leave (``window=True`` only).  Afterwards the scorer equals a fresh one over
         the remaining rows; captured request graphs are kept."""
         self.index.evict(m)
+
+    def delete(self, indices):
+        """``RetrievalIndex.delete`` plus the row store (the same call moves the survivors' ids and labels): the rows at the logical
+        positions ``indices`` leave (``window=True`` only).  Afterwards the scorer equals a fresh one over the remaining rows in age
+        order; captured request graphs are kept."""
+        self.index.delete(indices, self.pool_ids, self.pool_labels)
 
     def batch(self, ids):
         """-> data.DeviceBatch (idx [B, 1 + K, L], label_ids [B, 1 + K], y_true = zeros): what the model's forward consumes"""

@@ -1039,6 +1039,23 @@ def pool_evict(header, m, capacity, lib=None):
     lib.call("rat_pool_evict", _p(header), int(m), int(capacity), _stream(header))
 
 
+def pool_delete(db_t, header, indices, scratch, pool_ids=None, pool_labels=None, lib=None):
+    """the logical rows `indices` (int64, device, strictly ascending) of a ring leave; the survivors close up in place and in age order
+    in db_t, pool_ids and pool_labels, header = [n, head] -> [n - len(indices), head], all on the device.  `scratch`: int32, at least
+    capacity * max(F, L) elements (capacity * F without the row store).  An empty list launches nothing."""
+    lib = lib or get_lib()
+    _chk(db_t, torch.int32, "db_t"), _chk(header, torch.int64, "header"), _chk(indices, torch.int64, "indices")
+    _chk(scratch, torch.int32, "scratch"), _chk(pool_ids, torch.int32, "pool_ids"), _chk(pool_labels, name="pool_labels")
+    F, capacity = db_t.shape
+    assert header.numel() >= 2 and indices.ndim == 1 and (pool_ids is None) == (pool_labels is None)
+    L = F
+    if pool_ids is not None:
+        L = pool_ids.shape[1]
+        assert pool_ids.shape[0] == capacity and pool_labels.numel() == capacity
+    lib.call("rat_pool_delete", _p(db_t), _p(pool_ids), _p(pool_labels), _p(header), _p(indices), _p(scratch), scratch.numel() * 4,
+             indices.numel(), capacity, L, F, _stream(db_t))
+
+
 def bm25_topk_split_ring(db_t, header, qry_ids, qry_idf, topk, splits=0, lib=None):
     """bm25_topk_split over the header[0] live rows of the ring db_t int32 [F, capacity], oldest (slot header[1]) first; the indices
     returned are logical positions; splits = 0: chosen from the capacity"""
