@@ -424,6 +424,37 @@ int rat_batch_assemble_ring(const int32_t* data_ids, const float* data_labels, c
 int rat_pool_delete(int32_t* db_ids_field_major, int32_t* pool_ids, float* pool_labels, int64_t* header_dev, const int64_t* del_dev,
                     void* scratch, size_t scratch_bytes, int64_t n_del, int64_t capacity, int row_len, int n_fields, void* stream);
 
+/* A pool addressed by key (additive in ABI v9 as well): find the live rows that hold given ids, and relabel rows, on the device.
+ * Both take the pool in one of the three forms of the scan — pool_form RAT_POOL_HOST: n_rows live rows, given by value (header_dev is
+ * not read); RAT_POOL_DEV: n = header_dev[0]; RAT_POOL_RING: {n, head} = header_dev[0 .. 1], logical row i in slot head + i (wrapped).
+ * n is clamped to [0, capacity] and head to [0, capacity), as the ring scan clamps them; `capacity` is the number of rows (slots) the
+ * store holds (for an immutable pool: its N).
+ *
+ * rat_pool_find: word (slot, c) of the store is store[slot * row_stride + cols[c] * col_stride] — db_ids_field_major: row_stride 1,
+ * col_stride capacity (or N), store_cols n_fields; pool_ids: row_stride row_len, col_stride 1, store_cols row_len.  cols [n_cols] int32
+ * (device) are positions inside the store (clamped to [0, store_cols)), keys [n_keys][n_cols] int32 (device) are sorted
+ * lexicographically (signed) and distinct — the caller sorts.  Logical row i MATCHES if some key equals it on all n_cols columns.
+ * out_count[0] = the number of matching live rows (also when it exceeds max_out); out_idx[0 .. min(total, max_out)) = the first matches
+ * in ascending logical order; out_idx[min(total, max_out) .. max_out) = -1, so the list can be handed to rat_pool_set_labels whole.
+ * Three launches on the stream — count per range, offsets, ranked store — with no work-group waiting for another.  groups = 0: the
+ * number of ranges is chosen from the capacity alone (at most RAT_POOL_FIND_AUTO_GROUPS), so the grid does not depend on the live
+ * count and a find queues behind pushes, evictions and deletions; 1 .. 4096 forces that many (a range past the end is empty).
+ * workspace: 8 (2 groups + 1) bytes, 8-byte aligned (groups = 0: 8 (2 RAT_POOL_FIND_AUTO_GROUPS + 1) always suffices).  For ANY header
+ * and key content nothing outside the store, keys, out_idx[0 .. max_out), out_count and the workspace is addressed.
+ *
+ * rat_pool_set_labels: pool_labels[slot of logical indices[j]] = labels[j * label_stride] for j < m, one launch; label_stride 1 (a
+ * label per index) or 0 (labels[0] for all).  An index < 0 or >= n is skipped on the device.  Distinct indices are the caller's
+ * business (two entries for one row: either label stays).  m <= 0 launches nothing. */
+#define RAT_POOL_HOST 0
+#define RAT_POOL_DEV 1
+#define RAT_POOL_RING 2
+#define RAT_POOL_FIND_AUTO_GROUPS 1024
+int rat_pool_find(const int32_t* store, int64_t row_stride, int64_t col_stride, int store_cols, int pool_form, const int64_t* header_dev,
+                  int64_t n_rows, int64_t capacity, const int32_t* cols, int n_cols, const int32_t* keys, int64_t n_keys, int64_t* out_idx,
+                  int64_t max_out, int64_t* out_count, void* workspace, size_t workspace_bytes, int groups, void* stream);
+int rat_pool_set_labels(float* pool_labels, int pool_form, const int64_t* header_dev, int64_t n_rows, int64_t capacity,
+                        const int64_t* indices, const float* labels, int64_t m, int label_stride, void* stream);
+
 /* ---- K3: prediction head -----------------------------------------------------------------------------
  * Plain fp32 GEMM on MFMA for MLP_Layer's nn.Linear (deep.py:126-141) forward / dgrad / wgrad:
  * C[M][N] = op(A) op(B) (+ bias[N]) (+ beta*C), row-major with leading dimensions, op = transpose flag. */

@@ -25,6 +25,11 @@ RetrievalIndex over np.delete(pool, rows) — for m in {1, 64, 4096}, with the r
 appended again between rounds, untimed, so every round sees the same row count); (iii) replayed score() of one scorer at B in
 {1, 16, 256} immediately after a deletion of 4096 rows against immediately before it.  --delete --trace runs the deletions of (i)
 alone, a few per point, for a kernel trace taken in a run of its own: (ii), the device time of the delete launches.
+--find — the pool addressed by key instead (profiles/online/find_bench.txt), same geometry, clock and alternation, with the ring's head
+at 0 and wrapped: (i) OnlineScorer.find / RetrievalIndex.find of M in {1, 64, 4096} keys on one and on three columns against
+np.flatnonzero over a host copy of the pool (what a caller has to keep without it), and the device time of the three launches alone;
+(ii) relabel_where of one key against the only route there was, delete plus append of the corrected row; (iii) replayed score() at B in
+{1, 16, 256} immediately after a relabel_where against immediately before it, the same captured request.
 There is no CPU fallback: without a GPU the tool exits with an error."""
 import argparse
 import os
@@ -450,6 +455,126 @@ def part_delete(emit, quick, trace):
          % len(scorer._graphs))
 
 
+def _host_find(host, cols, keys):
+    """np.flatnonzero over a host copy of the pool's ids: np.isin on the first column, then whole key tuples on its candidates"""
+    cand = np.flatnonzero(np.isin(host[:, cols[0]], keys[:, 0]))
+    if len(cols) == 1:
+        return cand
+    void = np.dtype((np.void, 4 * len(cols)))
+    rows = np.ascontiguousarray(host[cand][:, cols]).view(void).ravel()
+    return cand[np.isin(rows, np.ascontiguousarray(keys).view(void).ravel())]
+
+
+def part_find(emit, quick):
+    from rat_amd import ops
+    from rat_amd.online import OnlineScorer
+    name, model, rows, vocab, cfg, n_pool, capacity = _movielens(quick)
+    dev, cols = torch.device("cuda:0"), cfg["used_col_indices"]
+    min_ms = 50.0 if quick else MIN_TIMED_MS                               # of timed work per point and side
+    pool = rows(n_pool)
+    rs = np.random.RandomState(5)
+    requests = {B: torch.from_numpy(np.stack([rs.randint(0, v, size=B) for v in vocab], axis=1).astype(np.int32)).to(dev)
+                for B in (1, 16, 256)}
+    scorer = OnlineScorer(model, pool, cfg, graph=True, capacity=capacity, window=True)
+    cur = pool
+    for B, ids in requests.items():
+        for _ in range(5):
+            scorer.score(ids)
+        torch.cuda.synchronize()
+    assert all(e[1] for e in scorer._graphs.values()) and len(scorer._graphs) == 3, "the requests were not captured"
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    for state in ("head = 0", "wrapped"):
+        if state == "wrapped":
+            cur = _wrap(scorer, rows, cur, n_pool, capacity)
+            n, head = scorer.index.count.cpu().tolist()
+            assert n == n_pool and head + n > capacity, (n, head)
+            emit("   after the pushes: n = %d, head = %d — %d live rows before the wrap, %d after it" % (n, head, capacity - head,
+                                                                                                      n - (capacity - head)))
+        host = np.ascontiguousarray(cur[:, :-1].astype(np.int32))          # the copy a caller keeps without find
+        emit("== find (i), %s: M keys (taken from live rows) on C columns over %d live rows (%d id columns) in a capacity of %d: "
+             "OnlineScorer.find (pool_ids) and RetrievalIndex.find (db_t) [ms per call, host clock + synchronise, the count read back "
+             "included] against np.flatnonzero over a host copy of the ids, alternating; then the device time of the three launches "
+             "alone [us per call, a hipGraph of %d calls, device events]" % (state, n_pool, host.shape[1], capacity, REPS))
+        for C in (1, 3):
+            cc = cols[:C]
+            for M in (1, 64, 4096):
+                keys = host[rs.choice(n_pool, M, replace=False)][:, cc].astype(np.int64)
+                want = _host_find(host, cc, keys.astype(np.int32))
+                for obj in (scorer, scorer.index):
+                    assert np.array_equal(obj.find(cc, keys).cpu().numpy(), want), (state, C, M)
+                per = {"OnlineScorer.find": [], "RetrievalIndex.find": [], "numpy": []}
+                while min(sum(v) for v in per.values()) < min_ms or min(len(v) for v in per.values()) < 3:
+                    per["OnlineScorer.find"].append(timed(lambda: scorer.find(cc, keys))[0])
+                    per["RetrievalIndex.find"].append(timed(lambda: scorer.index.find(cc, keys))[0])
+                    per["numpy"].append(timed(lambda: _host_find(host, cc, keys.astype(np.int32)))[0])
+                table = torch.from_numpy(np.unique(keys.astype(np.int32), axis=0)).to(dev)
+                pos = torch.from_numpy(np.arange(C, dtype=np.int32)).to(dev)
+                form = scorer.index._pool_form()
+                out = (torch.empty(capacity, dtype=torch.int64, device=dev), torch.empty(1, dtype=torch.int64, device=dev))
+                graphs = {"pool_ids": _graph_of(lambda: ops.pool_find(scorer.pool_ids, pos, table, False, out_idx=out[0], out_count=out[1],
+                                                                      max_out=n_pool, **form), REPS)[0],
+                          "db_t": _graph_of(lambda: ops.pool_find(scorer.index.db_t, pos, table, True, out_idx=out[0], out_count=out[1],
+                                                                  max_out=n_pool, **form), REPS)[0]}
+                dev_ms = time_alternating(graphs, REPS, min_ms / 5)
+                a, b, c = (sum(per[k]) / len(per[k]) for k in ("OnlineScorer.find", "RetrievalIndex.find", "numpy"))
+                emit("%-8s C %d M %5d  %6d matches | OnlineScorer.find %s | RetrievalIndex.find %s | numpy %s | numpy / find = %.1fx, %.1fx "
+                     "| device: pool_ids %.1f us, db_t %.1f us" % (state, C, M, len(want), _stats(per["OnlineScorer.find"]),
+                                                                  _stats(per["RetrievalIndex.find"]), _stats(per["numpy"]), c / a, c / b,
+                                                                  dev_ms["pool_ids"] * 1e3, dev_ms["db_t"] * 1e3))
+                del graphs
+
+        emit("== find (ii), %s: one row's label is corrected [ms per call]: relabel_where of its key (all %d id columns) against delete of "
+             "the row (its position known) plus append of the corrected row; host clock + synchronise, alternating" % (state, host.shape[1]))
+        per = {"relabel_where": [], "delete + append": []}
+        all_cols = list(range(host.shape[1]))
+        scorer.relabel_where(all_cols, np.full((1, host.shape[1]), -1), 0.0)       # nobody holds it: allocates the index list, untimed
+        while min(sum(v) for v in per.values()) < min_ms or min(len(v) for v in per.values()) < 3:
+            i = int(rs.randint(0, len(cur)))
+            key = cur[i:i + 1, :-1].astype(np.int64)
+            per["relabel_where"].append(timed(lambda: scorer.relabel_where(all_cols, key, 1.0 - cur[i, -1]))[0])
+            cur[_host_find(host, all_cols, key.astype(np.int32)), -1] = 1.0 - cur[i, -1]
+            j = int(rs.randint(0, len(cur)))
+            row = cur[j:j + 1].copy()
+            row[0, -1] = 1.0 - row[0, -1]
+
+            def old_route():
+                scorer.delete([j])
+                scorer.append(row)
+            per["delete + append"].append(timed(old_route)[0])
+            cur = np.concatenate([np.delete(cur, [j], axis=0), row])
+            host = np.ascontiguousarray(cur[:, :-1].astype(np.int32))
+        a, b = (sum(per[k]) / len(per[k]) for k in ("relabel_where", "delete + append"))
+        emit("%-8s | relabel_where %s | delete + append %s | delete + append / relabel_where = %.1fx" %
+             (state, _stats(per["relabel_where"]), _stats(per["delete + append"]), b / a))
+
+        emit("== find (iii), %s: replayed OnlineScorer.score() [us per request], %s: immediately after relabel_where(one key) against "
+             "immediately before it, the same scorer and the same captured request; host clock + synchronise, rounds of 200 requests, "
+             "before and after alternating" % (state, name))
+        for B, ids in requests.items():
+            per = {"before": [], "after": []}
+            while min(sum(v) for v in per.values()) * 200 / 1e3 < min_ms:
+                per["before"].append(_replay_round(scorer, ids))
+                i = int(rs.randint(0, len(cur)))
+                key = cur[i:i + 1, :-1].astype(np.int64)
+                scorer.relabel_where(all_cols, key, 1.0 - cur[i, -1])
+                cur[_host_find(host, all_cols, key.astype(np.int32)), -1] = 1.0 - cur[i, -1]
+                per["after"].append(_replay_round(scorer, ids))
+            a, b = (sum(per[k]) / len(per[k]) for k in ("after", "before"))
+            emit("%-8s B %4d | after %s | before %s | after / before = %.4f" % (state, B, _stats(per["after"]), _stats(per["before"]), a / b))
+        assert len(scorer._graphs) == 3 and all(e[1] for e in scorer._graphs.values()), "a relabel invalidated a captured request"
+    fresh = OnlineScorer(model, cur, cfg, graph=False)
+    assert torch.equal(scorer.score(requests[16]), fresh.score(requests[16])), "replay after the relabels != fresh scorer"
+    emit("   (the replayed request after the last relabel equals a fresh scorer over the modelled rows and labels, bit for bit; %d graphs kept)"
+         % len(scorer._graphs))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the report to this file")
@@ -457,6 +582,7 @@ def main():
     ap.add_argument("--append", action="store_true", help="measure the growing pool (append against a new index; replay with capacity)")
     ap.add_argument("--window", action="store_true", help="measure the sliding pool (replay with window=True; append on a full window)")
     ap.add_argument("--delete", action="store_true", help="measure deletion from the sliding pool (delete against a new index; replay)")
+    ap.add_argument("--find", action="store_true", help="measure the pool addressed by key (find against numpy; relabel; replay)")
     ap.add_argument("--trace", action="store_true", help="with --delete: only a few deletions per point, for a kernel trace")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -479,6 +605,9 @@ def main():
         return
     if args.delete:
         part_delete(emit, args.quick, args.trace)
+        return
+    if args.find:
+        part_find(emit, args.quick)
         return
     part1(emit, args.quick)
     part2(emit, args.quick)

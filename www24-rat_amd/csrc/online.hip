@@ -760,3 +760,242 @@ extern "C" int rat_pool_delete(int32_t* db_ids_field_major, int32_t* pool_ids, f
     RAT_LAUNCH(pool_delete_commit_kernel, 1u, 64, 0, stream, header_dev, n_del, capacity);
     return rat_check_launch("rat_pool_delete");
 }
+
+// ------------------------------------------------------------------------------------------------------------ a pool addressed by key
+// rat_pool_find: the logical indices (ascending) of the live rows that equal one of M keys on C columns.  One kernel serves both
+// stores through two strides — word (slot, c) is store[slot * row_stride + cols[c] * col_stride]: db_t has row stride 1 and column
+// stride capacity (or N), a wave reads 64 consecutive rows of a column; pool_ids has row stride L and column stride 1, the C columns
+// of a row share cache lines.  Three launches, kernel boundaries the only ordering between work-groups (as rat_pool_delete: nobody
+// waits on a flag, and the ORDER of the output needs no atomic):
+//   1  work-group g owns the logical range [g R, (g + 1) R), R = ceil(n / groups) from the row count read on the device (ranges past
+//      the end are empty); a thread looks its row up in the sorted key table (binary search) and the group's match count goes to ws[g]
+//   2  one work-group: exclusive offsets of the counts -> ws[groups + g], the total -> ws[2 groups] and out_count
+//   3  the same ranges, the same test: a shuffle scan over the wave and the waves' sums through LDS give every match its rank inside
+//      the group, and the logical index goes to out_idx[offset + rank] if that is < max_out; the grid then fills out_idx[min(total,
+//      max_out) .. max_out) with -1 — so the list can be handed on whole (rat_pool_set_labels skips -1), no count read back.
+// rat_pool_set_labels writes labels through the ring at such a list.
+namespace {
+
+constexpr int FIND_THREADS = 256;
+constexpr int FIND_WAVES = FIND_THREADS / 64;
+constexpr int FIND_MAX_COLS = 32;
+constexpr int FIND_MAX_GROUPS = 4096;
+// groups = 0: from the capacity only (the grid may not depend on the live count: a find queues behind pushes, evictions and
+// deletions) — four trips of a work-group per range at the full capacity, at most RAT_POOL_FIND_AUTO_GROUPS ranges
+constexpr int64_t FIND_AUTO_ROWS = 4 * FIND_THREADS;
+
+struct FindArgs {
+    const int32_t* store;
+    int64_t row_stride, col_stride;
+    const int64_t* header;   // POOL_DEV: {n}; POOL_RING: {n, head}; POOL_HOST: not read
+    int64_t N, capacity;     // N: the row count of POOL_HOST; capacity: the rows (slots) the store holds
+    const int32_t* cols;     // [C] positions inside the store, clamped to [0, store_cols)
+    const int32_t* keys;     // [M][C] sorted lexicographically (signed), distinct
+    int64_t M;
+    int C, store_cols, groups;
+    int64_t* out_idx;        // [max_out]
+    int64_t* out_count;      // [1]
+    int64_t max_out;
+    int64_t* ws;             // [groups] counts, [groups] exclusive offsets, [1] total
+};
+
+// the live rows as every launch sees them: n clamped to [0, capacity] and head to [0, capacity), as the ring scan clamps its header
+struct PoolView {
+    int64_t n, head;
+};
+template <int POOL>
+__device__ __forceinline__ PoolView pool_view(const int64_t* header, int64_t n_host, int64_t capacity) {
+    PoolView v{n_host, 0};
+    if constexpr (POOL != POOL_HOST) v.n = header[0];
+    v.n = v.n < 0 ? 0 : (v.n > capacity ? capacity : v.n);
+    if constexpr (POOL == POOL_RING) {
+        v.head = header[1];
+        v.head = v.head < 0 ? 0 : (v.head >= capacity ? capacity - 1 : v.head);
+    }
+    return v;
+}
+
+__device__ __forceinline__ int64_t find_col_offset(const FindArgs& a, int c) {     // wave-uniform: scalar loads
+    int64_t col = a.cols[c];
+    col = col < 0 ? 0 : (col >= a.store_cols ? a.store_cols - 1 : col);
+    return col * a.col_stride;
+}
+
+// Is the C-tuple of the row in `slot` one of the keys?  Lower bound of the tuple in the key table; column 0 of the row stays in a
+// register and decides almost every step, the others are read (again, from cache) only where column 0 ties.  mid stays in [0, M)
+// and the interval shrinks every step whatever the table holds: an unsorted table gives a wrong answer, never a wrong address.
+__device__ __forceinline__ bool find_row_matches(const FindArgs& a, int64_t slot) {
+    const int32_t* row = a.store + slot * a.row_stride;
+    const int32_t v0 = row[find_col_offset(a, 0)];
+    int64_t lo = 0, hi = a.M;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        const int32_t* key = a.keys + mid * a.C;
+        bool less = key[0] < v0, equal = key[0] == v0;
+        for (int c = 1; equal && c < a.C; ++c) {
+            const int32_t v = row[find_col_offset(a, c)];
+            less = key[c] < v;
+            equal = key[c] == v;
+        }
+        if (equal) return true;
+        if (less)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return false;
+}
+
+template <int POOL, bool WRITE>
+__global__ void __launch_bounds__(FIND_THREADS) pool_find_kernel(FindArgs a) {
+    __shared__ int wave_sum[FIND_WAVES];
+    const int tid = threadIdx.x, lane = rat_lane(), wave = rat_wave();
+    const PoolView v = pool_view<POOL>(a.header, a.N, a.capacity);
+    const int64_t R = (v.n + a.groups - 1) / a.groups;
+    const int64_t g = blockIdx.x;
+    const int64_t lo = g * R < v.n ? g * R : v.n;                              // ranges past the end of the pool are empty
+    const int64_t hi = lo + R < v.n ? lo + R : v.n;
+    [[maybe_unused]] int64_t base = 0;                                         // WRITE: where the trip's first match goes
+    if constexpr (WRITE) base = a.ws[a.groups + g];
+    int count = 0;
+    for (int64_t i0 = lo; i0 < hi; i0 += FIND_THREADS) {                       // the trip count is the same in every thread
+        const int64_t i = i0 + tid;
+        const int hit = i < hi && find_row_matches(a, ring_wrap(v.head + i, a.capacity)) ? 1 : 0;
+        if constexpr (!WRITE) {
+            count += hit;
+        } else {
+            int incl = hit;                                                    // matches of this wave up to and including this lane
+            for (int d = 1; d < 64; d <<= 1) {
+                const int below = __shfl(incl, (lane - d) & 63);
+                if (lane >= d) incl += below;
+            }
+            if (lane == 63) wave_sum[wave] = incl;
+            __syncthreads();
+            int before = 0, all = 0;
+            for (int w = 0; w < FIND_WAVES; ++w) {
+                const int s = wave_sum[w];
+                all += s;
+                before += w < wave ? s : 0;
+            }
+            const int64_t pos = base + before + incl - hit;
+            if (hit && pos < a.max_out) a.out_idx[pos] = i;
+            base += all;
+            __syncthreads();                                                   // the next trip reuses wave_sum
+        }
+    }
+    if constexpr (!WRITE) {
+        for (int d = 32; d > 0; d >>= 1) count += __shfl_xor(count, d);
+        if (lane == 0) wave_sum[wave] = count;
+        __syncthreads();
+        if (tid == 0) {
+            int64_t sum = 0;
+            for (int w = 0; w < FIND_WAVES; ++w) sum += wave_sum[w];
+            a.ws[g] = sum;
+        }
+    } else {
+        int64_t first = a.ws[2 * (int64_t)a.groups];                           // the total; the tail behind the matches is -1
+        first = first < 0 ? 0 : (first > a.max_out ? a.max_out : first);
+        for (int64_t j = first + g * FIND_THREADS + tid; j < a.max_out; j += (int64_t)gridDim.x * FIND_THREADS) a.out_idx[j] = -1;
+    }
+}
+
+// launch 2: thread t takes `per` consecutive counts; its offset is the sum of the threads' sums before it
+__global__ void __launch_bounds__(FIND_THREADS) pool_find_offsets_kernel(int64_t* ws, int64_t* out_count, int groups) {
+    __shared__ int64_t part[FIND_THREADS];
+    const int tid = threadIdx.x;
+    const int per = (groups + FIND_THREADS - 1) / FIND_THREADS;
+    const int g0 = tid * per < groups ? tid * per : groups;
+    const int g1 = g0 + per < groups ? g0 + per : groups;
+    int64_t sum = 0;
+    for (int g = g0; g < g1; ++g) sum += ws[g];
+    part[tid] = sum;
+    __syncthreads();
+    int64_t before = 0;
+    for (int t = 0; t < tid; ++t) before += part[t];
+    for (int g = g0; g < g1; ++g) {
+        ws[groups + g] = before;
+        before += ws[g];
+    }
+    if (tid == FIND_THREADS - 1) {                                             // the last thread's running sum is the total
+        ws[2 * (int64_t)groups] = before;
+        out_count[0] = before;
+    }
+}
+
+template <int POOL>
+int launch_find(const FindArgs& a, void* stream) {
+    RAT_LAUNCH((pool_find_kernel<POOL, false>), (unsigned)a.groups, FIND_THREADS, 0, stream, a);
+    if (rat_check_launch("rat_pool_find") != 0) return -1;
+    RAT_LAUNCH(pool_find_offsets_kernel, 1u, FIND_THREADS, 0, stream, a.ws, a.out_count, a.groups);
+    if (rat_check_launch("rat_pool_find") != 0) return -1;
+    RAT_LAUNCH((pool_find_kernel<POOL, true>), (unsigned)a.groups, FIND_THREADS, 0, stream, a);
+    return rat_check_launch("rat_pool_find");
+}
+
+struct SetLabelsArgs {
+    float* pool_labels;      // [capacity]
+    const int64_t* header;
+    const int64_t* indices;  // [m] logical; < 0 or >= n: skipped
+    const float* labels;     // [m], or [1] with label_stride = 0
+    int64_t N, capacity, m;
+    int label_stride;
+};
+
+template <int POOL>
+__global__ void __launch_bounds__(256) pool_set_labels_kernel(SetLabelsArgs a) {
+    const PoolView v = pool_view<POOL>(a.header, a.N, a.capacity);
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < a.m; j += (int64_t)gridDim.x * 256) {
+        const int64_t i = a.indices[j];
+        if (i >= 0 && i < v.n) a.pool_labels[ring_wrap(v.head + i, a.capacity)] = a.labels[j * a.label_stride];
+    }
+}
+
+}  // namespace
+
+extern "C" int rat_pool_find(const int32_t* store, int64_t row_stride, int64_t col_stride, int store_cols, int pool_form,
+                             const int64_t* header_dev, int64_t n_rows, int64_t capacity, const int32_t* cols, int n_cols,
+                             const int32_t* keys, int64_t n_keys, int64_t* out_idx, int64_t max_out, int64_t* out_count, void* workspace,
+                             size_t workspace_bytes, int groups, void* stream) {
+    RAT_REQUIRE(store && cols && keys && out_count && workspace, "null pointer");
+    RAT_REQUIRE(pool_form == POOL_HOST || pool_form == POOL_DEV || pool_form == POOL_RING, "pool_form must be 0, 1 or 2");
+    RAT_REQUIRE(pool_form == POOL_HOST || header_dev, "null header");
+    RAT_REQUIRE(capacity > 0 && row_stride > 0 && col_stride > 0 && store_cols > 0 && n_keys > 0 && max_out >= 0, "bad dims");
+    RAT_REQUIRE(pool_form != POOL_HOST || (n_rows >= 0 && n_rows <= capacity), "n_rows outside [0, capacity]");
+    RAT_REQUIRE(n_cols > 0 && n_cols <= FIND_MAX_COLS, "1 to 32 key columns are supported");
+    RAT_REQUIRE(max_out == 0 || out_idx, "null out_idx");
+    RAT_REQUIRE(groups >= 0 && groups <= FIND_MAX_GROUPS, "groups must be 0 (library's choice) or 1..4096");
+    if (groups == 0) {
+        const int64_t by_rows = (capacity + FIND_AUTO_ROWS - 1) / FIND_AUTO_ROWS;
+        groups = (int)(by_rows < RAT_POOL_FIND_AUTO_GROUPS ? by_rows : RAT_POOL_FIND_AUTO_GROUPS);
+    }
+    RAT_REQUIRE((capacity + groups - 1) / groups <= INT32_MAX, "more than 2^31 - 1 rows per range: pass more groups");
+    RAT_REQUIRE(workspace_bytes / sizeof(int64_t) >= 2 * (size_t)groups + 1, "workspace smaller than 8 (2 groups + 1) bytes");
+    RAT_REQUIRE(((uintptr_t)workspace & 7) == 0, "workspace must be 8-byte aligned");
+    FindArgs a{store, row_stride, col_stride, header_dev, n_rows, capacity, cols, keys, n_keys, n_cols, store_cols, groups,
+               out_idx, out_count, max_out, static_cast<int64_t*>(workspace)};
+    if (pool_form == POOL_HOST) return launch_find<POOL_HOST>(a, stream);
+    if (pool_form == POOL_DEV) return launch_find<POOL_DEV>(a, stream);
+    return launch_find<POOL_RING>(a, stream);
+}
+
+extern "C" int rat_pool_set_labels(float* pool_labels, int pool_form, const int64_t* header_dev, int64_t n_rows, int64_t capacity,
+                                   const int64_t* indices, const float* labels, int64_t m, int label_stride, void* stream) {
+    RAT_REQUIRE(pool_labels, "null pointer");
+    RAT_REQUIRE(pool_form == POOL_HOST || pool_form == POOL_DEV || pool_form == POOL_RING, "pool_form must be 0, 1 or 2");
+    RAT_REQUIRE(pool_form == POOL_HOST || header_dev, "null header");
+    RAT_REQUIRE(capacity > 0, "bad dims");
+    RAT_REQUIRE(pool_form != POOL_HOST || (n_rows >= 0 && n_rows <= capacity), "n_rows outside [0, capacity]");
+    RAT_REQUIRE(label_stride == 0 || label_stride == 1, "label_stride must be 1 (a label per index) or 0 (one label for all)");
+    if (m <= 0) return 0;                              // nothing to write: nothing is launched
+    RAT_REQUIRE(indices && labels, "null pointer");
+    SetLabelsArgs a{pool_labels, header_dev, indices, labels, n_rows, capacity, m, label_stride};
+    const int64_t blocks = (m + 255) / 256;
+    const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
+    if (pool_form == POOL_HOST)
+        RAT_LAUNCH(pool_set_labels_kernel<POOL_HOST>, grid, 256, 0, stream, a);
+    else if (pool_form == POOL_DEV)
+        RAT_LAUNCH(pool_set_labels_kernel<POOL_DEV>, grid, 256, 0, stream, a);
+    else
+        RAT_LAUNCH(pool_set_labels_kernel<POOL_RING>, grid, 256, 0, stream, a);
+    return rat_check_launch("rat_pool_set_labels");
+}

@@ -166,6 +166,10 @@ _SIGNATURES = {
     "rat_batch_assemble_ring": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_int, c_int, c_int, _P]),
     # a pool that loses rows: the survivors of a ring close up in place, staged through a scratch buffer
     "rat_pool_delete": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t, c_int64, c_int64, c_int, c_int, _P]),
+    # a pool addressed by key: the logical indices of the live rows that hold given ids, and labels written at such indices
+    "rat_pool_find": (c_int, [_P, c_int64, c_int64, c_int, c_int, _P, c_int64, c_int64, _P, c_int, _P, c_int64, _P, c_int64, _P, _P,
+                              c_size_t, c_int, _P]),
+    "rat_pool_set_labels": (c_int, [_P, c_int, _P, c_int64, c_int64, _P, _P, c_int64, c_int, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -36,6 +36,16 @@ on the first delete), every survivor's index drops by the number of deleted rows
 compacted the same way and the counts of the deleted rows leave the tables, so afterwards the object again answers exactly like a fresh
 one over the live rows in age order — and captured request graphs are kept, as the row count is read on the device.
 
+The pool is addressed by key as well as by position.  ``find(cols, keys)`` searches the live rows on the device for rows that equal one
+of ``keys`` on the columns ``cols`` (``rat_pool_find``: three launches through the ring, no host copy of the pool) and returns their
+logical positions in age order — ``RetrievalIndex.find`` over the used columns in ``db_t``, ``OnlineScorer.find`` over any id column in
+``pool_ids``.  ``OnlineScorer.set_labels(indices, labels)`` rewrites labels in place (``rat_pool_set_labels``): a label is in no IDF
+table, so nothing else moves, and captured request graphs read the new labels at their next replay.  ``relabel_where(cols, keys,
+label)`` chains the two on the stream without reading anything back — the list a find leaves is padded with ``-1``, which the label
+kernel skips — for the click that arrives after its impression; ``delete_where(cols, keys)`` (``window=True`` only) is ``find`` then
+``delete``, for the item that is taken down.  All of them serve the immutable, the ``capacity=`` and the ``window=True`` form (the
+deletion the last only), and afterwards the object answers exactly like a fresh one over the live rows with those labels.
+
 Not served online (refused at construction): exact-match columns (numbering the groups needs a host ``np.unique`` over pool and
 queries), label-wise retrieval, topK > 32, more than 32 retrieval columns, data-parallel models.  Rows are deleted from a
 ``window=True`` pool only: the append-only form reserves its IDF tables for the rows that can still come, which deletions would undo.
@@ -75,6 +85,51 @@ def _host_rows(rows, row_len):
         raise ValueError("rows have %d columns, the pool's rows have %d (%d ids and the label)" % (rows.shape[1], row_len + 1, row_len))
     as_int = rows[:, :-1].astype(int)
     return np.ascontiguousarray(retrieval._as_int32(as_int, "appended")), as_int, np.ascontiguousarray(rows[:, -1].astype(np.float32))
+
+
+def _key_table(cols, keys, where, what):
+    """what ``find`` takes -> (positions inside the store int32 [C], keys int32 [M, C] sorted lexicographically and distinct), on the
+    host, or ValueError.  ``where``: column number of the encoded row -> its position inside the store searched"""
+    c = np.asarray(cols)
+    if c.ndim != 1 or not 1 <= c.size <= MAX_COLS:
+        raise ValueError("find takes 1 to %d columns as a 1-D list, got shape %s" % (MAX_COLS, tuple(c.shape)))
+    if not np.issubdtype(c.dtype, np.integer):
+        raise ValueError("find takes integer column numbers, got dtype %s" % c.dtype)
+    c = [int(x) for x in c]
+    if len(set(c)) != len(c):
+        raise ValueError("find: repeated column in %s" % (c,))
+    if any(x not in where for x in c):
+        raise ValueError("find: column %s is not %s" % ([x for x in c if x not in where], what))
+    if torch.is_tensor(keys):
+        keys = keys.detach().cpu().numpy()
+    k = np.asarray(keys)
+    if k.ndim != 2 or k.shape[0] < 1:
+        raise ValueError("find takes keys as a non-empty [M, C] table (one row per key), got shape %s" % (tuple(k.shape),))
+    if k.shape[1] != len(c):
+        raise ValueError("find: keys are %d wide for %d columns" % (k.shape[1], len(c)))
+    if not np.issubdtype(k.dtype, np.integer):
+        raise ValueError("find takes integer keys, got dtype %s" % k.dtype)
+    k = np.unique(retrieval._as_int32(k, "key"), axis=0)                       # rows in lexicographic (signed) order, each once
+    return np.asarray([where[x] for x in c], dtype=np.int32), np.ascontiguousarray(k)
+
+
+def _row_list(indices, n, what):
+    """host-side logical row indices -> int64 [m] in the caller's order, or ValueError: integer dtype, inside [0, n), no duplicates"""
+    if torch.is_tensor(indices):
+        indices = indices.detach().cpu().numpy()
+    idx = np.atleast_1d(np.asarray(indices))
+    if idx.ndim != 1:
+        raise ValueError("%s takes a 1-D list of logical row indices, got shape %s" % (what, tuple(idx.shape)))
+    if idx.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    if not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError("%s takes integer row indices, got dtype %s" % (what, idx.dtype))
+    if idx.min() < 0 or idx.max() >= n:
+        raise ValueError("%s: index outside [0, %d), the live rows of the pool (a negative index does not count from the end)" % (what, n))
+    idx = idx.astype(np.int64)
+    if len(np.unique(idx)) != len(idx):
+        raise ValueError("%s: duplicate index" % what)
+    return np.ascontiguousarray(idx)
 
 
 class RetrievalIndex:
@@ -322,6 +377,42 @@ class RetrievalIndex:
         self._upload_tables()
 
 
+    # ---- addressed by key -----------------------------------------------------------------------------------------------
+    def _pool_form(self):
+        """where ops.pool_find / ops.pool_set_labels take the live rows from: the three forms of the scan"""
+        if self.capacity is None:
+            return dict(n_rows=self.n_db)
+        return dict(header=self.count, ring=self.window)
+
+    def _find(self, store, field_major, positions, keys):
+        dev = self.device
+        out_idx, out_count = ops.pool_find(store, torch.from_numpy(positions).to(dev), torch.from_numpy(keys).to(dev), field_major,
+                                           max_out=self.n_db, lib=self._lib, **self._pool_form())
+        return out_idx[:int(out_count.item())].clone()                         # the one read-back: the number of matches
+
+    def find(self, cols, keys):
+        """The logical positions (0 = the oldest live row, as ``retrieve`` returns them), ascending, of the live rows that equal one of
+        ``keys`` on the columns ``cols``: an int64 device tensor of exactly the matches.  ``cols``: column numbers of the encoded row,
+        as ``col_indices`` — among the index's used columns, the only ones it stores; ``keys``: [M, C] integers, M >= 1, C = len(cols)
+        <= 32, in any order, repeats allowed.  The search runs on the device (``rat_pool_find``) in every form of the index; sizing the
+        result costs one small device-to-host read of the match count, so this call SYNCHRONISES with the stream.  ValueError for a
+        column that is not a used column, a repeated column, C or M out of range, a wrong key width, a non-integer dtype, a key
+        outside int32."""
+        positions, table = _key_table(cols, keys, {c: f for f, c in enumerate(self._col_list)},
+                                      "a used column of this index (%s)" % (self._col_list,))
+        return self._find(self.db_t, True, positions, table)
+
+    def delete_where(self, cols, keys):
+        """``find(cols, keys)`` then ``delete`` of what it found (``window=True`` only) -> the number of rows removed.  No match
+        returns 0 and changes nothing; a match set that would empty the pool is refused by ``delete``, with nothing written."""
+        if not self.window:
+            raise ValueError("this index was built without window=True: rows cannot be deleted")
+        found = self.find(cols, keys)
+        if found.numel():
+            self.delete(found)
+        return int(found.numel())
+
+
 class _RequestGraph:
     """retrieve -> assemble -> eval forward of one request size as one linear hipGraph (one stream, no parallel branches)"""
 
@@ -382,6 +473,7 @@ class OnlineScorer:
         self.graph = bool(graph)
         self._consts = {}              # request size -> (rows = arange(B), labels = zeros(B))
         self._graphs = {}              # key -> [eager requests seen, _RequestGraph | False | None]
+        self._found = None             # relabel_where's index list (one entry per row the pool can hold), from its first call on
 
     # ------------------------------------------------------------------------------------------------------------------
     def _constants(self, B):
@@ -421,6 +513,74 @@ class OnlineScorer:
         positions ``indices`` leave (``window=True`` only).  Afterwards the scorer equals a fresh one over the remaining rows in age
         order; captured request graphs are kept."""
         self.index.delete(indices, self.pool_ids, self.pool_labels)
+
+    def find(self, cols, keys):
+        """``RetrievalIndex.find`` over the row store: the logical positions, ascending, of the live rows that equal one of ``keys``
+        ([M, C]) on ``cols`` — ANY of the L id columns of the encoded row, not only the retrieval columns.  An int64 device tensor of
+        exactly the matches; reading their number back SYNCHRONISES with the stream.  Same refusals."""
+        L = self.index.row_len
+        positions, table = _key_table(cols, keys, {c: c for c in range(L)}, "one of the %d id columns of the pool" % L)
+        return self.index._find(self.pool_ids, False, positions, table)
+
+    def _labels(self, labels, m):
+        """a scalar, or one label per index -> fp32 device tensor [1] or [m], converted as the constructor converts the pool's"""
+        if not torch.is_tensor(labels):
+            labels = torch.from_numpy(np.asarray(labels).astype(np.float32))       # (a 0-d array stays 0-d)
+        lab = labels.detach().to(self.device, torch.float32)
+        if lab.ndim == 0:
+            return lab.reshape(1)
+        if lab.ndim != 1 or lab.numel() != m:
+            raise ValueError("labels must be a scalar or one label per index ([%d]), got shape %s" % (m, tuple(lab.shape)))
+        return lab.contiguous()
+
+    def set_labels(self, indices, labels):
+        """The live rows at the logical positions ``indices`` get ``labels`` (a scalar for all, or [m], one per index) in place, in
+        every form of the pool (``rat_pool_set_labels``).  A label is in no IDF table: nothing else moves, no captured request graph is
+        touched, and the next request — eager or replayed — reads the new labels.  Ordered with the requests on the current stream.
+        Host-side indices (a list, numpy, a host tensor) are validated — ValueError, and nothing written, for a non-integer dtype, an
+        index outside [0, len(pool)) or a duplicate.  A DEVICE tensor is passed through unread, without a synchronisation: entries < 0
+        or >= len(pool) are skipped by the kernel (so the ``-1``-padded list of a find can be passed whole), and duplicates are the
+        caller's business."""
+        if torch.is_tensor(indices) and indices.is_cuda:
+            if indices.ndim != 1:
+                raise ValueError("set_labels takes a 1-D list of logical row indices, got shape %s" % (tuple(indices.shape),))
+            if indices.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+                raise ValueError("set_labels takes integer row indices, got dtype %s" % indices.dtype)
+            idx = indices.detach().to(self.device, torch.int64).contiguous()
+        else:
+            idx = torch.from_numpy(_row_list(indices, len(self.index), "set_labels")).to(self.device)
+        lab = self._labels(labels, idx.numel())
+        if idx.numel():
+            ops.pool_set_labels(self.pool_labels, idx, lab, lib=self._lib, **self.index._pool_form())
+
+    def relabel_where(self, cols, keys, label):
+        """Every live row that equals one of ``keys`` on ``cols`` (as ``find`` takes them) gets ``label`` (a scalar): the find and the
+        label kernel are chained on the current stream, with no read-back and no synchronisation of its own — the impression whose
+        click arrived.  Returns the number of rows relabelled as an int64 DEVICE tensor [1].  The list in between holds one entry per
+        row the pool can hold (8 bytes each, allocated on the first call and kept), so no match set is ever truncated."""
+        L = self.index.row_len
+        positions, table = _key_table(cols, keys, {c: c for c in range(L)}, "one of the %d id columns of the pool" % L)
+        if np.ndim(label) != 0:
+            raise ValueError("relabel_where takes one label for all matching rows, got shape %s" % (np.shape(label),))
+        lab = self._labels(label, 1)
+        dev, form = self.device, self.index._pool_form()
+        if self._found is None:                                                # outside every captured graph: no request reads it
+            self._found = torch.empty(self.pool_labels.numel(), dtype=torch.int64, device=dev)
+        _, count = ops.pool_find(self.pool_ids, torch.from_numpy(positions).to(dev), torch.from_numpy(table).to(dev), False,
+                                 out_idx=self._found, lib=self._lib, **form)
+        ops.pool_set_labels(self.pool_labels, self._found, lab, lib=self._lib, **form)
+        return count
+
+    def delete_where(self, cols, keys):
+        """``find(cols, keys)`` then ``delete`` of what it found (``window=True`` only) -> the number of rows removed: the item that is
+        taken down, the user who opts out.  No match returns 0 and changes nothing; a match set that would empty the pool is refused
+        by ``delete``, with nothing written."""
+        if not self.index.window:
+            raise ValueError("this scorer's pool was built without window=True: rows cannot be deleted")
+        found = self.find(cols, keys)
+        if found.numel():
+            self.delete(found)
+        return int(found.numel())
 
     def batch(self, ids):
         """-> data.DeviceBatch (idx [B, 1 + K, L], label_ids [B, 1 + K], y_true = zeros): what the model's forward consumes"""

@@ -1056,6 +1056,66 @@ def pool_delete(db_t, header, indices, scratch, pool_ids=None, pool_labels=None,
              indices.numel(), capacity, L, F, _stream(db_t))
 
 
+POOL_HOST, POOL_DEV, POOL_RING = 0, 1, 2               # rat_hip.h: where a kernel takes the pool's extent from
+POOL_FIND_AUTO_GROUPS = 1024                           # RAT_POOL_FIND_AUTO_GROUPS
+
+
+def _pool_form(header, ring, n_rows, capacity):
+    """(pool_form, n_rows) of rat_pool_find / rat_pool_set_labels: no header — the row count by value (default: all `capacity` rows);
+    a header — its first word, and with `ring` its second word as the slot of the oldest row"""
+    if header is None:
+        assert not ring
+        n_rows = capacity if n_rows is None else int(n_rows)
+        assert 0 <= n_rows <= capacity
+        return POOL_HOST, n_rows
+    _chk(header, torch.int64, "header")
+    assert header.numel() >= (2 if ring else 1)
+    return (POOL_RING if ring else POOL_DEV), 0
+
+
+def pool_find(store, cols, keys, field_major, header=None, ring=False, n_rows=None, max_out=None, groups=0, out_idx=None,
+              out_count=None, lib=None):
+    """-> (out_idx int64 [max_out], out_count int64 [1]), on the device: the logical indices of the live rows of `store` that equal one
+    of `keys` (int32 [M, C], sorted lexicographically and distinct) on the store's columns `cols` (int32 [C]), ascending, then -1;
+    out_count is the number of matches even when max_out (default: the rows the store holds) is smaller.  `store`: int32
+    [F, capacity] (field_major, as db_t) or [capacity, L] (as pool_ids).  The pool's form as in _pool_form.  groups = 0: the number of
+    row ranges is chosen from the capacity."""
+    lib = lib or get_lib()
+    _chk(store, torch.int32, "store"), _chk(cols, torch.int32, "cols"), _chk(keys, torch.int32, "keys")
+    assert store.ndim == 2 and keys.ndim == 2 and cols.ndim == 1 and keys.shape[1] == cols.numel() and keys.shape[0] >= 1
+    if field_major:
+        (store_cols, capacity), row_stride, col_stride = store.shape, 1, store.shape[1]
+    else:
+        (capacity, store_cols), row_stride, col_stride = store.shape, store.shape[1], 1
+    form, n_rows = _pool_form(header, ring, n_rows, capacity)
+    dev = store.device
+    if out_idx is None:
+        out_idx = torch.empty(capacity if max_out is None else int(max_out), dtype=torch.int64, device=dev)
+    if out_count is None:
+        out_count = torch.empty(1, dtype=torch.int64, device=dev)
+    _chk(out_idx, torch.int64, "out_idx"), _chk(out_count, torch.int64, "out_count")
+    max_out = out_idx.numel() if max_out is None else int(max_out)
+    assert 0 <= max_out <= out_idx.numel() and out_count.numel() >= 1
+    ws = torch.empty(2 * (int(groups) or POOL_FIND_AUTO_GROUPS) + 1, dtype=torch.int64, device=dev)
+    lib.call("rat_pool_find", _p(store), row_stride, col_stride, store_cols, form, _p(header), n_rows, capacity, _p(cols), cols.numel(),
+             _p(keys), keys.shape[0], _p(out_idx), max_out, _p(out_count), _p(ws), ws.numel() * 8, int(groups), _stream(store))
+    return out_idx, out_count
+
+
+def pool_set_labels(pool_labels, indices, labels, header=None, ring=False, n_rows=None, lib=None):
+    """pool_labels[slot of logical indices[j]] = labels[j] (labels fp32 [m]) or labels[0] (fp32 [1]: one value for all), on the device;
+    indices int64 [m], entries < 0 or >= the live row count are skipped (the -1 tail of pool_find's list).  The pool's form as in
+    _pool_form."""
+    lib = lib or get_lib()
+    _chk(pool_labels, name="pool_labels"), _chk(indices, torch.int64, "indices"), _chk(labels, name="labels")
+    m = indices.numel()
+    assert indices.ndim == 1 and labels.numel() in (1, m)
+    capacity = pool_labels.numel()
+    form, n_rows = _pool_form(header, ring, n_rows, capacity)
+    lib.call("rat_pool_set_labels", _p(pool_labels), form, _p(header), n_rows, capacity, _p(indices), _p(labels), m,
+             0 if labels.numel() == 1 else 1, _stream(pool_labels))
+
+
 def bm25_topk_split_ring(db_t, header, qry_ids, qry_idf, topk, splits=0, lib=None):
     """bm25_topk_split over the header[0] live rows of the ring db_t int32 [F, capacity], oldest (slot header[1]) first; the indices
     returned are logical positions; splits = 0: chosen from the capacity"""
