@@ -342,6 +342,15 @@ int rat_bm25_query_prepare(const int32_t* ids, const int32_t* cols, const int32_
                            const int64_t* table_offsets, int32_t* qry_ids, double* qry_idf, int64_t n_qry, int row_stride,
                            int n_fields, void* stream);
 
+/* The same for a batch that holds SEVERAL requests, each of them one query batch of the reference: first_row [n_qry] int64 (device)
+ * gives, for batch row q, the batch row that opens q's request, and the dtype rule above looks at THAT row instead of row 0 — so every
+ * request gets the weights it would get alone, whoever shares the launch.  first_row[q] is clamped to [0, n_qry) on the device: a
+ * corrupt array gives a wrong weight, never an address outside `ids`.  With first_row all zero this is rat_bm25_query_prepare.
+ * One launch on `stream`, no allocation, no synchronisation, no atomics: capturable.  (Additive in ABI v9.) */
+int rat_bm25_query_prepare_seg(const int32_t* ids, const int64_t* first_row, const int32_t* cols, const int32_t* table_ids,
+                               const double* table_idf, const int64_t* table_offsets, int32_t* qry_ids, double* qry_idf, int64_t n_qry,
+                               int row_stride, int n_fields, void* stream);
+
 /* rat_bm25_topk's contract (same inputs, same outputs, same tie rule, same limits) for FEW queries: the pool is cut into `splits`
  * contiguous row ranges of ceil(n_db / splits) rows scanned by different work-groups (ranges past the end are empty), each leaves its
  * topk best in `workspace` ([n_qry][splits][topk] float64 scores, then as many int64 indices), and a second launch merges them by

@@ -30,6 +30,10 @@ at 0 and wrapped: (i) OnlineScorer.find / RetrievalIndex.find of M in {1, 64, 40
 np.flatnonzero over a host copy of the pool (what a caller has to keep without it), and the device time of the three launches alone;
 (ii) relabel_where of one key against the only route there was, delete plus append of the corrected row; (iii) replayed score() at B in
 {1, 16, 256} immediately after a relabel_where against immediately before it, the same captured request.
+--requests — requests that share a launch instead (profiles/online/requests_bench.txt), the immutable 1.4 M-row pool: (i) R in
+{1, 4, 16, 64, 256} single-row requests as ONE OnlineScorer.score_requests call against R consecutive replayed score() calls on the same
+scorer (each side issues its launches and synchronises once at the end of the R requests); (ii) score_requests with one request of B
+rows against score() of the same B at B in {1, 16, 256}: what the segment array and the padding cost.  Same clock and alternation.
 There is no CPU fallback: without a GPU the tool exits with an error."""
 import argparse
 import os
@@ -575,6 +579,71 @@ def part_find(emit, quick):
          % len(scorer._graphs))
 
 
+def part_requests(emit, quick):
+    from rat_amd.online import OnlineScorer
+    name, model, rows, vocab, cfg, n_pool, _capacity = _movielens(quick)
+    dev = torch.device("cuda:0")
+    min_s = 0.05 if quick else MIN_TIMED_MS / 1e3
+    pool = rows(n_pool)
+    rs = np.random.RandomState(5)
+    scorer = OnlineScorer(model, pool, cfg, graph=True)
+
+    def request_rows(B):
+        return torch.from_numpy(np.stack([rs.randint(0, v, size=B) for v in vocab], axis=1).astype(np.int32)).to(dev)
+
+    def rounds(sides, calls):
+        """sides: {label: fn} -> {label: [us per call of every round]}; a round is `calls` calls, each followed by a synchronise"""
+        per = {k: [] for k in sides}
+        while min(sum(v) for v in per.values()) * calls / 1e6 < min_s or min(len(v) for v in per.values()) < 3:
+            for label, fn in sides.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    fn()
+                    torch.cuda.synchronize()
+                per[label].append((time.perf_counter() - t0) / calls * 1e6)
+        return per
+
+    emit("== requests (i): R single-row requests [us for all R], %s, %d-row pool: ONE score_requests call (ids on the device, offsets on the "
+         "host) against R consecutive replayed score() calls on the same scorer; host clock, one synchronise after the R requests, the "
+         "sides alternating round by round" % (name, n_pool))
+    for R in (1, 4, 16, 64, 256):
+        ids = request_rows(R)
+        singles = [ids[r:r + 1].contiguous() for r in range(R)]
+        off = np.arange(R + 1, dtype=np.int64)
+        for _ in range(5):
+            y, _ = scorer.score_requests((ids, off))
+            y_alone = torch.cat([scorer.score(x) for x in singles])
+        torch.cuda.synchronize()
+        assert all(e[1] for e in scorer._bucket_graphs.values()) and all(e[1] for e in scorer._graphs.values()), "not captured"
+        worst = float((y - y_alone).abs().max())
+
+        def alone():
+            for x in singles:
+                scorer.score(x)
+        per = rounds({"score_requests": lambda: scorer.score_requests((ids, off)), "score": alone}, max(2, 256 // R))
+        a, b = (sum(per[k]) / len(per[k]) for k in ("score_requests", "score"))
+        emit("R %4d | score_requests %s | R x score %s | R x score / score_requests = %.2fx | worst |dy| %.1e, bit-equal: %s"
+             % (R, _stats(per["score_requests"]), _stats(per["score"]), b / a, worst, torch.equal(y, y_alone)))
+
+    emit("== requests (ii): ONE request of B rows [us per request]: score_requests (segment array, padding to the bucket) against replayed "
+         "score() of the same B; host clock + synchronise, rounds of 200 requests alternating")
+    for B in (1, 16, 256):
+        ids = request_rows(B)
+        off = np.array([0, B], dtype=np.int64)
+        for _ in range(5):
+            y, _ = scorer.score_requests((ids, off))
+            y_plain = scorer.score(ids)
+        torch.cuda.synchronize()
+        assert torch.equal(y, y_plain), "one request through score_requests != score()"
+        per = rounds({"score_requests": lambda: scorer.score_requests((ids, off)), "score": lambda: scorer.score(ids)}, 200)
+        a, b = (sum(per[k]) / len(per[k]) for k in ("score_requests", "score"))
+        lo, hi = min(per["score"]), max(per["score"])
+        emit("B %4d | score_requests %s | score %s | score_requests / score = %.4f | inside score()'s min .. max: %s"
+             % (B, _stats(per["score_requests"]), _stats(per["score"]), a / b, lo <= a <= hi))
+    emit("   (%d bucket graphs, %d score() graphs)" % (len(scorer._bucket_graphs), len(scorer._graphs)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the report to this file")
@@ -583,6 +652,7 @@ def main():
     ap.add_argument("--window", action="store_true", help="measure the sliding pool (replay with window=True; append on a full window)")
     ap.add_argument("--delete", action="store_true", help="measure deletion from the sliding pool (delete against a new index; replay)")
     ap.add_argument("--find", action="store_true", help="measure the pool addressed by key (find against numpy; relabel; replay)")
+    ap.add_argument("--requests", action="store_true", help="measure requests that share a launch (score_requests against R x score)")
     ap.add_argument("--trace", action="store_true", help="with --delete: only a few deletions per point, for a kernel trace")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -608,6 +678,9 @@ def main():
         return
     if args.find:
         part_find(emit, args.quick)
+        return
+    if args.requests:
+        part_requests(emit, args.quick)
         return
     part1(emit, args.quick)
     part2(emit, args.quick)

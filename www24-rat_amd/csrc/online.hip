@@ -378,6 +378,7 @@ struct PrepArgs {
     double* qry_idf;         // [Q][F]
     int64_t Q;
     int row_stride, F;
+    const int64_t* first_row;  // [Q], SEG only: the batch row that opens row q's request
 };
 
 // np.searchsorted(vals, x) clipped to the last entry, then vals[pos] == x (retrieval.map_data_to_idf): -> position or -1
@@ -393,6 +394,9 @@ __device__ __forceinline__ int64_t table_find(const int32_t* vals, int64_t n, in
     return lo < n && vals[lo] == x ? lo : -1;
 }
 
+// SEG: the batch holds several requests, each one query batch of the reference — the dtype rule of row q looks at the first row of
+// ITS request, first_row[q] (clamped to [0, Q): a corrupt array gives a wrong weight, never an address outside `ids`)
+template <bool SEG>
 __global__ void __launch_bounds__(256) bm25_query_prepare_kernel(PrepArgs a) {
     const int64_t total = a.Q * a.F;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
@@ -405,7 +409,12 @@ __global__ void __launch_bounds__(256) bm25_query_prepare_kernel(PrepArgs a) {
         const int64_t pos = table_find(vals, n, x);
         double w = pos >= 0 ? idf[pos] : 0.0;
         // the reference's np.vectorize takes the column's dtype from the batch's FIRST row: a miss there makes the column int64
-        if (table_find(vals, n, a.ids[a.cols[f]]) < 0) w = (double)(int64_t)w;
+        int64_t first = 0;
+        if constexpr (SEG) {
+            first = a.first_row[q];
+            first = first < 0 ? 0 : (first < a.Q ? first : a.Q - 1);
+        }
+        if (table_find(vals, n, a.ids[first * a.row_stride + a.cols[f]]) < 0) w = (double)(int64_t)w;
         a.qry_ids[e] = x;
         a.qry_idf[e] = w;
     }
@@ -419,10 +428,22 @@ extern "C" int rat_bm25_query_prepare(const int32_t* ids, const int32_t* cols, c
     RAT_REQUIRE(ids && cols && table_ids && table_idf && table_offsets && qry_ids && qry_idf, "null pointer");
     RAT_REQUIRE(n_qry > 0 && n_fields > 0 && row_stride > 0, "bad dims");
     RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
-    PrepArgs a{ids, cols, table_ids, table_idf, table_offsets, qry_ids, qry_idf, n_qry, row_stride, n_fields};
+    PrepArgs a{ids, cols, table_ids, table_idf, table_offsets, qry_ids, qry_idf, n_qry, row_stride, n_fields, nullptr};
     const int64_t blocks = (n_qry * n_fields + 255) / 256;
-    RAT_LAUNCH(bm25_query_prepare_kernel, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
+    RAT_LAUNCH(bm25_query_prepare_kernel<false>, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
     return rat_check_launch("rat_bm25_query_prepare");
+}
+
+extern "C" int rat_bm25_query_prepare_seg(const int32_t* ids, const int64_t* first_row, const int32_t* cols, const int32_t* table_ids,
+                                          const double* table_idf, const int64_t* table_offsets, int32_t* qry_ids, double* qry_idf,
+                                          int64_t n_qry, int row_stride, int n_fields, void* stream) {
+    RAT_REQUIRE(ids && first_row && cols && table_ids && table_idf && table_offsets && qry_ids && qry_idf, "null pointer");
+    RAT_REQUIRE(n_qry > 0 && n_fields > 0 && row_stride > 0, "bad dims");
+    RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
+    PrepArgs a{ids, cols, table_ids, table_idf, table_offsets, qry_ids, qry_idf, n_qry, row_stride, n_fields, first_row};
+    const int64_t blocks = (n_qry * n_fields + 255) / 256;
+    RAT_LAUNCH(bm25_query_prepare_kernel<true>, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a);
+    return rat_check_launch("rat_bm25_query_prepare_seg");
 }
 
 extern "C" size_t rat_bm25_topk_split_workspace(int64_t n_qry, int topk, int splits) {

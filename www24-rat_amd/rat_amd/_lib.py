@@ -153,6 +153,7 @@ _SIGNATURES = {
     "rat_sparse_reduce_scalar_pool": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
     # the request path (rat_amd/online.py): query-side IDF mapping and the top-K scan split over pool ranges
     "rat_bm25_query_prepare": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, _P]),
+    "rat_bm25_query_prepare_seg": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, _P]),
     "rat_bm25_topk_split_workspace": (c_size_t, [c_int64, c_int, c_int]),
     "rat_bm25_topk_split": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_size_t, c_int64, c_int64, c_int, c_int, c_int, _P]),
     # a pool that grows in place: device-side append, and the scan / the assembly with the row count read from device memory

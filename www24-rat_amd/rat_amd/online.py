@@ -46,6 +46,14 @@ kernel skips — for the click that arrives after its impression; ``delete_where
 ``delete``, for the item that is taken down.  All of them serve the immutable, the ``capacity=`` and the ``window=True`` form (the
 deletion the last only), and afterwards the object answers exactly like a fresh one over the live rows with those labels.
 
+Requests can share a launch.  ``score_requests(requests)`` concatenates R independent requests to B rows and sends them through ONE
+chain of launches, each request answered exactly as if it had been sent alone: the only step of the chain in which a row looks at
+another row is the mapping's dtype rule, and ``rat_bm25_query_prepare_seg`` takes it from the first row of the row's OWN request
+(``first_row`` [B], derived from the request offsets; the scan, the merge and the assembly work query by query already).  With
+``graph=True`` the batch is padded to the next power of two — the pad rows are a trailing request of their own, copies of the batch's
+first row, whose outputs are dropped — so 13 captured graphs serve every request mix of every total up to 4096 rows; ids and
+``first_row`` live in static buffers refreshed before each replay.  ``score()`` and its graphs are untouched.
+
 Not served online (refused at construction): exact-match columns (numbering the groups needs a host ``np.unique`` over pool and
 queries), label-wise retrieval, topK > 32, more than 32 retrieval columns, data-parallel models.  Rows are deleted from a
 ``window=True`` pool only: the append-only form reserves its IDF tables for the rows that can still come, which deletions would undo.
@@ -71,6 +79,54 @@ def _as_device_ids(ids, device):
     if ids.dtype != torch.int32:
         ids = ids.to(torch.int32)
     return ids.contiguous()
+
+
+def _request_offsets(offsets, B):
+    """what ``retrieve(ids, request_offsets)`` takes -> (int64 [R + 1] on the host, None) for host-side offsets, validated — 1-D,
+    integer dtype, from 0 to B, strictly ascending, or ValueError — or (None, the device tensor as int64), passed through UNREAD: no
+    synchronisation, and the kernel clamps what it derives from it"""
+    if torch.is_tensor(offsets) and offsets.is_cuda:
+        if offsets.ndim != 1 or offsets.numel() < 2:
+            raise ValueError("request_offsets must be a 1-D list of R + 1 row offsets, got shape %s" % (tuple(offsets.shape),))
+        if offsets.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+            raise ValueError("request_offsets must be integers, got dtype %s" % offsets.dtype)
+        return None, offsets.detach().to(torch.int64).contiguous()
+    if torch.is_tensor(offsets):
+        offsets = offsets.detach().numpy()
+    off = np.asarray(offsets)
+    if off.ndim != 1 or off.size < 2:
+        raise ValueError("request_offsets must be a 1-D list of R + 1 row offsets, got shape %s" % (tuple(off.shape),))
+    if not np.issubdtype(off.dtype, np.integer):
+        raise ValueError("request_offsets must be integers, got dtype %s" % off.dtype)
+    off = off.astype(np.int64)
+    if off[0] != 0:
+        raise ValueError("request_offsets must start at 0, got %d" % off[0])
+    if off[-1] != B:
+        raise ValueError("request_offsets must end at the number of rows (%d), got %d" % (B, off[-1]))
+    steps = np.diff(off)
+    if (steps < 0).any():
+        raise ValueError("request_offsets must be ascending")
+    if (steps == 0).any():
+        raise ValueError("empty request (request %d has no rows)" % int(np.nonzero(steps == 0)[0][0]))
+    return np.ascontiguousarray(off), None
+
+
+def _first_rows(off_host, off_dev, B, device, pad_to=None, upload=True):
+    """request offsets -> first_row int64 [B]: for every batch row the row that opens its request.  ``pad_to`` > B: rows
+    B .. pad_to - 1 are one more request, which starts at row B.  Host offsets: built on the host (``upload=False`` returns that
+    numpy array), one upload; device offsets: a search on the device, nothing read back"""
+    P = B if pad_to is None else pad_to
+    if off_host is not None:
+        first = np.repeat(off_host[:-1], np.diff(off_host))
+        if P > B:
+            first = np.concatenate([first, np.full(P - B, B, dtype=np.int64)])
+        return torch.from_numpy(first).to(device, non_blocking=True) if upload else first
+    rows = torch.arange(B, dtype=torch.int64, device=device)
+    req = (torch.searchsorted(off_dev, rows, right=True) - 1).clamp_(0, off_dev.numel() - 1)
+    first = off_dev[req]
+    if P > B:
+        first = torch.cat([first, torch.full((P - B,), B, dtype=torch.int64, device=device)])
+    return first.contiguous()
 
 
 def _host_rows(rows, row_len):
@@ -187,16 +243,23 @@ class RetrievalIndex:
         self.table_idf = up(np.concatenate([w for _, w in tables]).astype(np.float64))
         self.table_offsets = up(np.concatenate([[0], np.cumsum([len(v) for v, _ in tables])]).astype(np.int64))
 
-    def retrieve(self, ids):
+    def retrieve(self, ids, request_offsets=None, _first_row=None):
         """ids [B, L] (full encoded rows) -> (values fp64 [B, K], indices int64 [B, K] with -1 padding, lens int64 [B]), on the device.
         With ``window=True`` the indices are LOGICAL positions (0 = the oldest live row, len(index) - 1 = the newest): they hold until
-        the next eviction (an ``evict``, or an ``append`` into a full window) or ``delete``, which renumber the rows."""
+        the next eviction (an ``evict``, or an ``append`` into a full window) or ``delete``, which renumber the rows.
+        ``request_offsets`` (int64 [R + 1], ascending from 0 to B; host or device): rows [off[r], off[r + 1]) are request r, and the
+        result is the row-wise concatenation of ``retrieve(request_r)`` — one chain of launches for all of them.  Host-side offsets
+        are validated (ValueError, nothing launched: not 1-D, not integer, not from 0 to B, not ascending, an empty request); device
+        offsets are used unread, without a synchronisation."""
         ids = _as_device_ids(ids, self.device)
         if ids.shape[1] != self.row_len:
             raise ValueError("ids have %d columns, the pool's rows have %d" % (ids.shape[1], self.row_len))
         if ids.shape[0] == 0:
             raise ValueError("empty request")
-        qry_ids, qry_idf = ops.bm25_query_prepare(ids, self.cols, self.table_ids, self.table_idf, self.table_offsets, lib=self._lib)
+        if request_offsets is not None:
+            _first_row = _first_rows(*_request_offsets(request_offsets, ids.shape[0]), ids.shape[0], self.device)
+        qry_ids, qry_idf = ops.bm25_query_prepare(ids, self.cols, self.table_ids, self.table_idf, self.table_offsets,
+                                                  first_row=_first_row, lib=self._lib)
         if self.window:
             return ops.bm25_topk_split_ring(self.db_t, self.count, qry_ids, qry_idf, self.topK, splits=self.splits, lib=self._lib)
         if self.capacity is not None:
@@ -431,6 +494,33 @@ class _RequestGraph:
         return self.y_pred.clone()
 
 
+class _BucketGraph:
+    """the same chain for P rows (a power of two) that hold ANY mix of requests: ids and first_row are static inputs, refreshed before
+    each replay; linear on one stream like _RequestGraph"""
+
+    def __init__(self, scorer, ids, first_row):
+        self.static_ids, self.static_first = ids.clone(), first_row.clone()
+        self._first_host = None        # the host array static_first was last uploaded from
+        self._stream = torch.cuda.Stream(device=ids.device)
+        self.graph = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        with torch.no_grad(), torch.cuda.graph(self.graph, stream=self._stream, capture_error_mode="thread_local"):
+            self.y_pred = scorer._score_eager(self.static_ids, self.static_first)
+
+    def run(self, ids, first_row):
+        """first_row: a device tensor, or the host array it is built from — uploaded straight into the static buffer, and not at all
+        when it equals the last one (the same request sizes again: a batcher with fixed slots, one request of B rows)"""
+        self.static_ids.copy_(ids, non_blocking=True)
+        if torch.is_tensor(first_row):
+            self._first_host = None
+            self.static_first.copy_(first_row, non_blocking=True)
+        elif self._first_host is None or not np.array_equal(first_row, self._first_host):
+            self._first_host = first_row                                       # (kept: the upload reads it)
+            self.static_first.copy_(torch.from_numpy(first_row), non_blocking=True)
+        self.graph.replay()
+        return self.y_pred
+
+
 class OnlineScorer:
     """``score(ids)``: fp32 [B] predictions of a trained model for fresh encoded rows ``ids`` [B, L], the neighbours retrieved from
     ``pool_array`` ([N, L + 1], label last) on the spot.  ``retrieval_configs`` is the dataset's block (``topK``, ``used_cols`` or
@@ -473,6 +563,7 @@ class OnlineScorer:
         self.graph = bool(graph)
         self._consts = {}              # request size -> (rows = arange(B), labels = zeros(B))
         self._graphs = {}              # key -> [eager requests seen, _RequestGraph | False | None]
+        self._bucket_graphs = {}       # score_requests: (bucket, ...) -> [eager calls seen, _BucketGraph | False | None]
         self._found = None             # relabel_where's index list (one entry per row the pool can hold), from its first call on
 
     # ------------------------------------------------------------------------------------------------------------------
@@ -483,9 +574,9 @@ class OnlineScorer:
                                    torch.zeros(B, dtype=torch.float32, device=self.device))
         return c
 
-    def _assemble(self, ids):
+    def _assemble(self, ids, first_row=None):
         rows, labels = self._constants(ids.shape[0])
-        _values, indices, _lens = self.index.retrieve(ids)
+        _values, indices, _lens = self.index.retrieve(ids, _first_row=first_row)
         # the request is the query table, the kernel's own index output the neighbour lists; -1 keeps its numpy meaning, as offline
         if self.index.window:                                                  # ... logical positions in the ring, -1 its newest row
             return ops.batch_assemble_ring(ids, labels, self.pool_ids, self.pool_labels, indices, rows, self.index.count, lib=self._lib)
@@ -493,8 +584,8 @@ class OnlineScorer:
             return ops.batch_assemble_dev(ids, labels, self.pool_ids, self.pool_labels, indices, rows, self.index.count, lib=self._lib)
         return ops.batch_assemble(ids, labels, self.pool_ids, self.pool_labels, indices, rows, lib=self._lib)
 
-    def _score_eager(self, ids):
-        y_pred, _loss, _reg, _saved = self.model._run_forward(self._assemble(ids), save=False, with_reg=False)
+    def _score_eager(self, ids, first_row=None):
+        y_pred, _loss, _reg, _saved = self.model._run_forward(self._assemble(ids, first_row), save=False, with_reg=False)
         return y_pred.reshape(-1)
 
     def append(self, rows):
@@ -593,6 +684,86 @@ class OnlineScorer:
         with torch.no_grad():
             g = self._graph_for(ids)
             return g.run(ids) if g is not None else self._score_eager(ids)
+
+    # ---- requests that share a launch ------------------------------------------------------------------------------------
+    def _requests(self, requests):
+        """a list of [B_r, L] id arrays, or a pair (ids [B, L], request_offsets) -> (ids int32 [B, L] on the device, host offsets
+        int64 [R + 1] | None, device offsets | None), or ValueError"""
+        if isinstance(requests, tuple) and len(requests) == 2:                 # a TUPLE of two is the pair, a list holds requests
+            ids = _as_device_ids(requests[0], self.device)
+            off_host, off_dev = _request_offsets(requests[1], ids.shape[0])
+        else:
+            if len(requests) == 0:
+                raise ValueError("empty request list")
+            parts = [r if torch.is_tensor(r) else torch.from_numpy(np.ascontiguousarray(np.asarray(r))) for r in requests]
+            for k, r in enumerate(parts):
+                if r.ndim != 2:
+                    raise ValueError("request %d must be [B_r, L] encoded rows, got shape %s" % (k, tuple(r.shape)))
+                if r.shape[1] != self.index.row_len:
+                    raise ValueError("request %d has %d columns, the pool's rows have %d" % (k, r.shape[1], self.index.row_len))
+                if r.shape[0] == 0:
+                    raise ValueError("empty request (request %d has no rows)" % k)
+            if any(r.is_cuda for r in parts) or len({r.dtype for r in parts}) > 1:
+                parts = [_as_device_ids(r, self.device) for r in parts]
+            ids = _as_device_ids(torch.cat(parts), self.device)                # host arrays of one dtype: one upload for all of them
+            off_host, off_dev = np.concatenate([[0], np.cumsum([r.shape[0] for r in parts])]).astype(np.int64), None
+        if ids.shape[1] != self.index.row_len:
+            raise ValueError("ids have %d columns, the pool's rows have %d" % (ids.shape[1], self.index.row_len))
+        if ids.shape[0] == 0:
+            raise ValueError("empty request")
+        return ids, off_host, off_dev
+
+    def batch_requests(self, requests):
+        """``batch()`` for requests that share a launch (as ``score_requests`` takes them) -> data.DeviceBatch over all B rows, equal
+        to the concatenation of the per-request ``batch(request_r)``"""
+        ids, off_host, off_dev = self._requests(requests)
+        return DeviceBatch(*self._assemble(ids, _first_rows(off_host, off_dev, ids.shape[0], self.device)))
+
+    def score_requests(self, requests):
+        """R independent requests in one chain of launches, each answered as if it had been sent alone to ``score``.  ``requests``: a
+        LIST of [B_r, L] id arrays, or a pair — a TUPLE (ids [B, L], request_offsets int64 [R + 1] ascending from 0 to B, host or device).
+        Returns (y_pred fp32 [B] in input order, request_offsets int64 [R + 1] — a host tensor, or the device tensor that was passed):
+        request r's predictions are ``y_pred[off[r]:off[r + 1]]``.  With ``graph=True`` the batch is padded to the next power of two
+        (<= ``graph_max_batch``) with a trailing request of copies of its first row, whose outputs are dropped; after ``graph_warmup``
+        eager calls of a bucket its chain is captured and serves every request mix of that bucket."""
+        if self.model.training:
+            raise RuntimeError("OnlineScorer.score_requests needs the model in eval mode (model.eval())")
+        ids, off_host, off_dev = self._requests(requests)
+        B = ids.shape[0]
+        offsets = torch.from_numpy(off_host) if off_host is not None else off_dev
+        with torch.no_grad():
+            P = 1 << (B - 1).bit_length()
+            if not (self.graph and ids.is_cuda and P <= self.graph_max_batch):
+                return self._score_eager(ids, _first_rows(off_host, off_dev, B, self.device)), offsets
+            first_row = _first_rows(off_host, off_dev, B, self.device, pad_to=P, upload=False)
+            if P > B:                                                          # the pad rows: valid ids, a request of their own
+                ids = torch.cat([ids, ids[:1].expand(P - B, -1)])
+            g = self._bucket_graph_for(ids, first_row)
+            if g is not None:
+                return g.run(ids, first_row)[:B].clone(), offsets
+            return self._score_eager(ids, self._on_device(first_row))[:B].clone(), offsets
+
+    def _on_device(self, first_row):
+        return first_row if torch.is_tensor(first_row) else torch.from_numpy(first_row).to(self.device, non_blocking=True)
+
+    def _bucket_graph_for(self, ids, first_row):
+        P = ids.shape[0]
+        key = (P, self.model._eval_graph_key((P, self.index.topK + 1, ids.shape[1])))
+        entry = self._bucket_graphs.get(key)
+        if entry is None:
+            entry = self._bucket_graphs[key] = [0, None]
+        if entry[1] is None:
+            entry[0] += 1
+            if entry[0] <= self.graph_warmup:
+                return None
+            try:
+                entry[1] = _BucketGraph(self, ids, self._on_device(first_row))
+            except Exception as exc:
+                import logging
+                logging.warning("hipGraph capture of the batched online requests failed (%s: %s); continuing with eager launches",
+                                type(exc).__name__, exc)
+                entry[1] = False
+        return entry[1] or None
 
     def _graph_for(self, ids):
         B = ids.shape[0]

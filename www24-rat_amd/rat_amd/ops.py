@@ -928,9 +928,11 @@ def owner_scatter(dense_a, dense_b, extra_out, lists, stride, world, cap_a, cap_
 
 
 # ----------------------------------------------------------------------------- K6b: the request path (rat_amd/online.py)
-def bm25_query_prepare(ids, cols, table_ids, table_idf, table_offsets, lib=None):
+def bm25_query_prepare(ids, cols, table_ids, table_idf, table_offsets, first_row=None, lib=None):
     """ids int32 [Q, L] (full encoded rows) -> (qry_ids int32 [Q, F], qry_idf fp64 [Q, F]): retrieval.map_data_to_idf of ONE query
-    batch against the pool's IDF tables (flat: sorted ids int32, weights fp64, offsets int64 [F + 1]), all on the device"""
+    batch against the pool's IDF tables (flat: sorted ids int32, weights fp64, offsets int64 [F + 1]), all on the device.
+    ``first_row`` int64 [Q] (device): the batch holds several requests, row q belongs to the one that starts at row first_row[q], and
+    every request is mapped as a query batch of its own (rat_bm25_query_prepare_seg)"""
     lib = lib or get_lib()
     _chk(ids, torch.int32, "ids"), _chk(cols, torch.int32, "cols"), _chk(table_ids, torch.int32, "table_ids")
     _chk(table_idf, torch.float64, "table_idf"), _chk(table_offsets, torch.int64, "table_offsets")
@@ -939,6 +941,12 @@ def bm25_query_prepare(ids, cols, table_ids, table_idf, table_offsets, lib=None)
     assert table_offsets.numel() == F + 1
     qry_ids = torch.empty((Q, F), dtype=torch.int32, device=ids.device)
     qry_idf = torch.empty((Q, F), dtype=torch.float64, device=ids.device)
+    if first_row is not None:
+        _chk(first_row, torch.int64, "first_row")
+        assert first_row.numel() == Q
+        lib.call("rat_bm25_query_prepare_seg", _p(ids), _p(first_row), _p(cols), _p(table_ids), _p(table_idf), _p(table_offsets),
+                 _p(qry_ids), _p(qry_idf), Q, L, F, _stream(ids))
+        return qry_ids, qry_idf
     lib.call("rat_bm25_query_prepare", _p(ids), _p(cols), _p(table_ids), _p(table_idf), _p(table_offsets), _p(qry_ids), _p(qry_idf),
              Q, L, F, _stream(ids))
     return qry_ids, qry_idf
