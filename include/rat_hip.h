@@ -464,6 +464,33 @@ int rat_pool_find(const int32_t* store, int64_t row_stride, int64_t col_stride, 
 int rat_pool_set_labels(float* pool_labels, int pool_form, const int64_t* header_dev, int64_t n_rows, int64_t capacity,
                         const int64_t* indices, const float* labels, int64_t m, int label_stride, void* stream);
 
+/* A pool that looks at itself (additive in ABI v9 as well): score live rows against only the rows OLDER than them — what the
+ * reference's <X>-fold retrieval does for a self-pool (fuxictr/pytorch/data_generator.py:115-176).  The pool keeps its rows in age
+ * order (logical 0 = the oldest), so the horizon of a row is one number: its own logical index.  Both take the pool in the three
+ * forms above (pool_form, header_dev, n_rows, capacity; n clamped to [0, capacity], head to [0, capacity)).
+ *
+ * rat_pool_gather_rows: out_ids[j][0 .. row_len) and out_labels[j] = ids and label of the logical row indices[j] (int64, device) out
+ * of pool_ids [capacity][row_len] / pool_labels [capacity], one launch; an index < 0 or >= n gives a row of zeros and label 0.
+ * out_before[j] = indices[j] clamped to [0, n]: the row's horizon, which rat_bm25_topk_split_before consumes — nothing is read back
+ * in between.  n_indices <= 0 launches nothing.
+ *
+ * rat_bm25_topk_split_before: rat_bm25_topk_split's two launches with a horizon per query — query q's candidates are the logical
+ * rows i < before_dev[q] (int64 [n_qry], device; clamped to [0, n] on the device: a negative value or 0 gives lens 0, values 0 and
+ * indices -1, a value past the end the whole pool; no value gives an address outside the buffers).  db_ids_field_major is
+ * [n_fields][capacity] (RAT_POOL_HOST: the first n_rows columns are the pool).  For every q the values, indices and lens equal
+ * rat_bm25_topk over a contiguous copy of the logical rows [0, min(before[q], n)) with the same qry_idf, bit for bit: the scan scores
+ * every row as rat_bm25_topk_split does and a row at or past the horizon then scores 0; the lists, the merge and the total order
+ * (score descending, logical index ascending) are unchanged.  The IDF weights are the caller's: rat_bm25_query_prepare maps them from
+ * the tables of the WHOLE live pool.  Ranges are cut over [0, n); splits = 0 is chosen from the capacity in every form, so a captured
+ * launch never changes shape; workspace as rat_bm25_topk_split_workspace(n_qry, topk, splits). */
+int rat_pool_gather_rows(const int32_t* pool_ids, const float* pool_labels, int pool_form, const int64_t* header_dev, int64_t n_rows,
+                         int64_t capacity, const int64_t* indices, int32_t* out_ids, float* out_labels, int64_t* out_before,
+                         int64_t n_indices, int row_len, void* stream);
+int rat_bm25_topk_split_before(const int32_t* db_ids_field_major, int pool_form, const int64_t* header_dev, int64_t n_rows,
+                               int64_t capacity, const int32_t* qry_ids, const double* qry_idf, const int64_t* before_dev,
+                               double* out_values, int64_t* out_indices, int64_t* out_lens, void* workspace, size_t workspace_bytes,
+                               int64_t n_qry, int n_fields, int topk, int splits, void* stream);
+
 /* ---- K3: prediction head -----------------------------------------------------------------------------
  * Plain fp32 GEMM on MFMA for MLP_Layer's nn.Linear (deep.py:126-141) forward / dgrad / wgrad:
  * C[M][N] = op(A) op(B) (+ bias[N]) (+ beta*C), row-major with leading dimensions, op = transpose flag. */

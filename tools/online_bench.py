@@ -34,6 +34,12 @@ np.flatnonzero over a host copy of the pool (what a caller has to keep without i
 {1, 4, 16, 64, 256} single-row requests as ONE OnlineScorer.score_requests call against R consecutive replayed score() calls on the same
 scorer (each side issues its launches and synchronises once at the end of the R requests); (ii) score_requests with one request of B
 rows against score() of the same B at B in {1, 16, 256}: what the segment array and the padding cost.  Same clock and alternation.
+--rows — the pool that looks at itself instead (profiles/online/rows_bench.txt), same geometry: (i) the scan alone, device time per call
+as in part 1 (hipGraphs of REPS calls, device events, the sides alternating): rat_bm25_topk_split_before with before = n for every
+query — the horizon excludes nothing, so the same rows are scored and the same lists come out — against the plain scan of the same
+pool form (immutable, capacity, window with the ring wrapped) at Q in {1, 16, 256}: what the compare and select per (row, query)
+cost; (ii) replayed score_rows(B indices) against replayed score(the same rows' ids) at B in {1, 16, 256}, host clock + synchronise,
+rounds of 200 alternating: what the gather and the horizon cost a request.
 There is no CPU fallback: without a GPU the tool exits with an error."""
 import argparse
 import os
@@ -644,6 +650,76 @@ def part_requests(emit, quick):
     emit("   (%d bucket graphs, %d score() graphs)" % (len(scorer._bucket_graphs), len(scorer._graphs)))
 
 
+def part_rows(emit, quick):
+    from rat_amd import ops
+    from rat_amd.online import OnlineScorer, RetrievalIndex
+    name, model, rows, vocab, cfg, n_pool, capacity = _movielens(quick)
+    dev, K, cols = torch.device("cuda:0"), cfg["topK"], cfg["used_col_indices"]
+    min_s = 0.05 if quick else MIN_TIMED_MS / 1e3
+    pool = rows(n_pool)
+    rs = np.random.RandomState(13)
+    emit("== rows (i): the scan alone [us per call, device time], %d-row pool (%d columns), K = %d: rat_bm25_topk_split_before with before = n "
+         "for every query against the plain split scan of the same pool form, splits = 0 on both sides; hipGraphs of %d calls, device "
+         "events, alternating" % (n_pool, len(cols), K, REPS))
+    wrap = n_pool // 3
+    forms = (("immutable", {}, 0), ("capacity", dict(capacity=capacity), 0), ("window wrapped", dict(capacity=n_pool + wrap, window=True), 2 * wrap))
+    for label, kw, pushes in forms:
+        index = RetrievalIndex(pool, cols, K, dev, **kw)
+        for _ in range(pushes // wrap):                                       # the window fills, then loses its oldest rows: the head moves
+            index.append(rows(wrap))
+        if pushes:
+            assert int(index.count[1]) + len(index) > index.capacity, "the window does not wrap"
+        n = len(index)
+        form = index._pool_form()
+        for Q in (1, 16, 256):
+            ids = torch.from_numpy(np.stack([rs.randint(0, v, size=Q) for v in vocab], axis=1).astype(np.int32)).to(dev)
+            q_ids, q_idf = ops.bm25_query_prepare(ids, index.cols, index.table_ids, index.table_idf, index.table_offsets)
+            before = torch.full((Q,), n, dtype=torch.int64, device=dev)
+            if index.window:
+                plain = lambda: ops.bm25_topk_split_ring(index.db_t, index.count, q_ids, q_idf, K)          # noqa: E731
+            elif index.capacity is not None:
+                plain = lambda: ops.bm25_topk_split_dev(index.db_t, index.count, q_ids, q_idf, K)           # noqa: E731
+            else:
+                plain = lambda: ops.bm25_topk_split(index.db_t, q_ids, q_idf, K)                            # noqa: E731
+            horizon = lambda: ops.bm25_topk_split_before(index.db_t, q_ids, q_idf, before, K, **form)        # noqa: E731
+            want, got = plain(), horizon()
+            torch.cuda.synchronize()
+            for g, w in zip(got, want):
+                assert torch.equal(g.view(torch.int64), w.view(torch.int64)), (label, Q)
+            graphs = {"plain": _graph_of(plain, REPS)[0], "before = n": _graph_of(horizon, REPS)[0]}
+            ms = time_alternating(graphs, REPS, 50.0 if quick else MIN_TIMED_MS)
+            emit("%-14s Q %4d | plain %.1f | before = n %.1f | before / plain = %.4f" %
+                 (label, Q, ms["plain"] * 1e3, ms["before = n"] * 1e3, ms["before = n"] / ms["plain"]))
+            del graphs
+        del index
+
+    emit("== rows (ii): replayed OnlineScorer.score_rows(B indices) against replayed score(the same rows' ids) [us per request], %s, "
+         "immutable %d-row pool; host clock + synchronise, rounds of 200 requests alternating" % (name, n_pool))
+    scorer = OnlineScorer(model, pool, cfg, graph=True)
+    for B in (1, 16, 256):
+        idx = torch.from_numpy(rs.choice(n_pool, size=B, replace=False).astype(np.int64)).to(dev)
+        ids = scorer.pool_ids[idx].contiguous()
+        for _ in range(5):
+            y_rows, y_plain = scorer.score_rows(idx), scorer.score(ids)
+        torch.cuda.synchronize()
+        assert all(e[1] for e in scorer._rows_graphs.values()) and all(e[1] for e in scorer._graphs.values()), "not captured"
+        per = {"score_rows": [], "score": []}
+        while min(sum(v) for v in per.values()) * 200 / 1e6 < min_s or min(len(v) for v in per.values()) < 3:
+            per["score_rows"].append(_replay_round(_RowsSide(scorer), idx))
+            per["score"].append(_replay_round(scorer, ids))
+        a, b = (sum(per[k]) / len(per[k]) for k in ("score_rows", "score"))
+        emit("B %4d | score_rows %s | score %s | score_rows / score = %.4f | predictions differ (the row no longer sees itself): %s"
+             % (B, _stats(per["score_rows"]), _stats(per["score"]), a / b, not torch.equal(y_rows, y_plain)))
+    emit("   (%d score_rows graphs, %d score() graphs)" % (len(scorer._rows_graphs), len(scorer._graphs)))
+
+
+class _RowsSide:
+    """score_rows behind the name _replay_round calls"""
+
+    def __init__(self, scorer):
+        self.score = scorer.score_rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the report to this file")
@@ -653,6 +729,7 @@ def main():
     ap.add_argument("--delete", action="store_true", help="measure deletion from the sliding pool (delete against a new index; replay)")
     ap.add_argument("--find", action="store_true", help="measure the pool addressed by key (find against numpy; relabel; replay)")
     ap.add_argument("--requests", action="store_true", help="measure requests that share a launch (score_requests against R x score)")
+    ap.add_argument("--rows", action="store_true", help="measure the pool that looks at itself (horizon scan against the plain scan; score_rows)")
     ap.add_argument("--trace", action="store_true", help="with --delete: only a few deletions per point, for a kernel trace")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -681,6 +758,9 @@ def main():
         return
     if args.requests:
         part_requests(emit, args.quick)
+        return
+    if args.rows:
+        part_rows(emit, args.quick)
         return
     part1(emit, args.quick)
     part2(emit, args.quick)

@@ -105,6 +105,7 @@ struct SplitArgs {
     const int64_t* n_dev;    // POOL_DEV: the pool's current row count (the header a RetrievalIndex with capacity keeps);
                              // POOL_RING: that header is two words, {row count, physical slot of the oldest live row}
     int64_t stride;          // POOL_DEV / POOL_RING: column stride of db_t (the capacity); otherwise the stride is N
+    const int64_t* before;   // [Q], HORIZON only: query q sees the logical rows i < before[q]
 };
 
 // Where the scan takes the pool's extent from.
@@ -116,7 +117,13 @@ struct SplitArgs {
 // Everything after the prologue is the same code, so the same fp64 sums in the same order and the same merge.
 enum { POOL_HOST = 0, POOL_DEV = 1, POOL_RING = 2 };
 
-template <int KMAX, int QT, int RU, int POOL>
+// HORIZON (rat_bm25_topk_split_before): query q's candidates are the logical rows below before[q], clamped to [0, N] on the device.
+// The rows are scored as ever and a row at or past its query's horizon then scores 0 — one compare and select per (row, query) after
+// the field loop — so it never enters a list; what follows (insertion, wave merge, ranking, bm25_merge_kernel) is the same code, and
+// the sums, their order and the total order are those of the plain scan over the rows [0, before[q]).  Ranges are still cut over
+// [0, N), and a work-group whose range lies past every horizon of its tile scans it all the same (nothing here is tuned).
+// POOL_HOST with HORIZON takes the column stride from a.stride (the pool's capacity), the row count from a.N.
+template <int KMAX, int QT, int RU, int POOL, bool HORIZON>
 __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a) {
     __shared__ WaveTile<QT> tile_s[ON_WAVES];
     __shared__ double wl_v[ON_WAVES][QT][KMAX];          // the K best of every wave, ranked against each other after the barrier
@@ -134,6 +141,10 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
         head = a.n_dev[1];
         head = head < 0 ? 0 : (head >= stride ? stride - 1 : head);
     }
+    if constexpr (HORIZON && POOL == POOL_HOST) {
+        stride = a.stride;
+        N = N < 0 ? 0 : (N > stride ? stride : N);
+    }
     const int64_t chunk = (N + a.splits - 1) / a.splits;
     int parity = 0;
     for (int64_t item = blockIdx.x; item < ntiles * a.splits; item += gridDim.x) {
@@ -141,6 +152,15 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
         const int split = (int)(item % a.splits);
         const int64_t lo = split * chunk < N ? split * chunk : N;            // ranges past the end of the pool are empty
         const int64_t hi = lo + chunk < N ? lo + chunk : N;
+        [[maybe_unused]] int64_t bef[QT];                  // HORIZON: the tile's horizons, clamped to [0, N]
+        if constexpr (HORIZON) {
+#pragma unroll
+            for (int t = 0; t < QT; ++t) {
+                const int64_t q = q0 + t < a.Q ? q0 + t : a.Q - 1;            // wave-uniform: scalar loads
+                const int64_t b = a.before[q];
+                bef[t] = b < 0 ? 0 : (b > N ? N : b);
+            }
+        }
         double val[QT][KMAX], kth[QT];                     // kth = score of the current K-th entry (0 while the list is not full)
         int64_t idx[QT][KMAX];
 #pragma unroll
@@ -180,6 +200,12 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
 #pragma unroll
                     for (int u = 0; u < RU; ++u) s[u][t] += (qid == id[u] && n0 + (int64_t)u * ON_THREADS < hi) ? w : 0.0;
                 }
+            }
+            if constexpr (HORIZON) {
+#pragma unroll
+                for (int u = 0; u < RU; ++u)
+#pragma unroll
+                    for (int t = 0; t < QT; ++t) s[u][t] = n0 + (int64_t)u * ON_THREADS < bef[t] ? s[u][t] : 0.0;
             }
 #pragma unroll
             for (int u = 0; u < RU; ++u) {                                                // rows in increasing order
@@ -331,10 +357,10 @@ int64_t auto_splits(int64_t n_qry, int64_t n_db, int topk) {
 
 // the three entry points of the split scan: the same two launches, the scan instantiated with the row count by value, from the device,
 // or with the ring's header from the device
-template <int POOL>
+template <int POOL, bool HORIZON = false>
 int launch_split(const char* who, const int32_t* db_t, const int32_t* qry_ids, const double* qry_idf, double* out_values,
                  int64_t* out_indices, int64_t* out_lens, void* workspace, size_t workspace_bytes, int64_t n_db, const int64_t* n_dev,
-                 int64_t stride, int64_t n_qry, int n_fields, int topk, int splits, void* stream) {
+                 int64_t stride, int64_t n_qry, int n_fields, int topk, int splits, void* stream, const int64_t* before = nullptr) {
     const size_t need = (size_t)n_qry * (size_t)splits * (size_t)topk * (sizeof(double) + sizeof(int64_t));
     if (workspace == nullptr || workspace_bytes < need)
         return rat_fail(std::string(who) + ": workspace smaller than rat_bm25_topk_split_workspace()");
@@ -355,12 +381,13 @@ int launch_split(const char* who, const int32_t* db_t, const int32_t* qry_ids, c
     a.splits = splits;
     a.n_dev = n_dev;
     a.stride = stride;
+    a.before = before;
     if (topk <= 8) {
         const int64_t items = (n_qry + 3) / 4 * splits;
-        RAT_LAUNCH((bm25_scan_split_kernel<8, 4, 4, POOL>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
+        RAT_LAUNCH((bm25_scan_split_kernel<8, 4, 4, POOL, HORIZON>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
     } else {
         const int64_t items = n_qry * splits;
-        RAT_LAUNCH((bm25_scan_split_kernel<32, 1, 4, POOL>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
+        RAT_LAUNCH((bm25_scan_split_kernel<32, 1, 4, POOL, HORIZON>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
     }
     if (rat_check_launch(who) != 0) return -1;
     RAT_LAUNCH(bm25_merge_kernel, (unsigned)(n_qry < 65536 ? n_qry : 65536), 64, 0, stream, a);
@@ -1019,4 +1046,91 @@ extern "C" int rat_pool_set_labels(float* pool_labels, int pool_form, const int6
     else
         RAT_LAUNCH(pool_set_labels_kernel<POOL_RING>, grid, 256, 0, stream, a);
     return rat_check_launch("rat_pool_set_labels");
+}
+
+// ------------------------------------------------------------------------------------------------------------ a pool that looks at itself
+// rat_pool_gather_rows: ids and labels of the logical rows indices[B] out of the row store, through the pool form, and every row's
+// own logical index — its horizon: the rows older than it — for rat_bm25_topk_split_before, which scans with that horizon per query.
+// The two are chained on a stream with nothing read back in between.
+namespace {
+
+struct GatherRowsArgs {
+    const int32_t* pool_ids;     // [capacity][L]
+    const float* pool_labels;    // [capacity]
+    const int64_t* header;
+    const int64_t* indices;      // [B] logical; < 0 or >= n: a row of zeros, label 0
+    int32_t* out_ids;            // [B][L]
+    float* out_labels;           // [B]
+    int64_t* out_before;         // [B] indices[j] clamped to [0, n]
+    int64_t N, capacity, B;
+    int L;
+};
+
+// work item e = word (j, c) of out_ids: consecutive lanes copy consecutive words of a row; the lane of a row's first word also
+// writes its label and its horizon
+template <int POOL>
+__global__ void __launch_bounds__(256) pool_gather_rows_kernel(GatherRowsArgs a) {
+    const PoolView v = pool_view<POOL>(a.header, a.N, a.capacity);
+    const int64_t total = a.B * a.L;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t j = e / a.L;
+        const int c = (int)(e % a.L);
+        const int64_t i = a.indices[j];
+        const bool live = i >= 0 && i < v.n;
+        const int64_t slot = live ? ring_wrap(v.head + i, a.capacity) : 0;
+        a.out_ids[e] = live ? a.pool_ids[slot * a.L + c] : 0;
+        if (c == 0) {
+            a.out_labels[j] = live ? a.pool_labels[slot] : 0.0f;
+            a.out_before[j] = i < 0 ? 0 : (i > v.n ? v.n : i);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int rat_pool_gather_rows(const int32_t* pool_ids, const float* pool_labels, int pool_form, const int64_t* header_dev,
+                                    int64_t n_rows, int64_t capacity, const int64_t* indices, int32_t* out_ids, float* out_labels,
+                                    int64_t* out_before, int64_t n_indices, int row_len, void* stream) {
+    RAT_REQUIRE(pool_ids && pool_labels, "null pointer");
+    RAT_REQUIRE(pool_form == POOL_HOST || pool_form == POOL_DEV || pool_form == POOL_RING, "pool_form must be 0, 1 or 2");
+    RAT_REQUIRE(pool_form == POOL_HOST || header_dev, "null header");
+    RAT_REQUIRE(capacity > 0 && row_len > 0, "bad dims");
+    RAT_REQUIRE(pool_form != POOL_HOST || (n_rows >= 0 && n_rows <= capacity), "n_rows outside [0, capacity]");
+    if (n_indices <= 0) return 0;                      // nothing to gather: nothing is launched
+    RAT_REQUIRE(indices && out_ids && out_labels && out_before, "null pointer");
+    GatherRowsArgs a{pool_ids, pool_labels, header_dev, indices, out_ids, out_labels, out_before, n_rows, capacity, n_indices, row_len};
+    const int64_t blocks = (n_indices * row_len + 255) / 256;
+    const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
+    if (pool_form == POOL_HOST)
+        RAT_LAUNCH(pool_gather_rows_kernel<POOL_HOST>, grid, 256, 0, stream, a);
+    else if (pool_form == POOL_DEV)
+        RAT_LAUNCH(pool_gather_rows_kernel<POOL_DEV>, grid, 256, 0, stream, a);
+    else
+        RAT_LAUNCH(pool_gather_rows_kernel<POOL_RING>, grid, 256, 0, stream, a);
+    return rat_check_launch("rat_pool_gather_rows");
+}
+
+extern "C" int rat_bm25_topk_split_before(const int32_t* db_ids_field_major, int pool_form, const int64_t* header_dev, int64_t n_rows,
+                                          int64_t capacity, const int32_t* qry_ids, const double* qry_idf, const int64_t* before_dev,
+                                          double* out_values, int64_t* out_indices, int64_t* out_lens, void* workspace,
+                                          size_t workspace_bytes, int64_t n_qry, int n_fields, int topk, int splits, void* stream) {
+    RAT_REQUIRE(db_ids_field_major && qry_ids && qry_idf && before_dev && out_values && out_indices && out_lens, "null pointer");
+    RAT_REQUIRE(pool_form == POOL_HOST || pool_form == POOL_DEV || pool_form == POOL_RING, "pool_form must be 0, 1 or 2");
+    RAT_REQUIRE(pool_form == POOL_HOST || header_dev, "null header");
+    RAT_REQUIRE(capacity > 0 && n_qry > 0 && n_fields > 0 && topk > 0, "bad dims");
+    RAT_REQUIRE(pool_form != POOL_HOST || (n_rows >= 0 && n_rows <= capacity), "n_rows outside [0, capacity]");
+    RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
+    RAT_REQUIRE(topk <= ON_KMAX, "topK > 32 is not supported");
+    RAT_REQUIRE(splits >= 0 && splits <= ON_MAX_SPLITS, "splits must be 0 (library's choice) or 1..4096");
+    // from the capacity in every form, as rat_bm25_topk_split_dev: one range too goes through the split kernel, which has the horizon
+    if (splits == 0) splits = (int)auto_splits(n_qry, capacity, topk);
+    const char* who = "rat_bm25_topk_split_before";
+    if (pool_form == POOL_HOST)
+        return launch_split<POOL_HOST, true>(who, db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
+                                             workspace_bytes, n_rows, nullptr, capacity, n_qry, n_fields, topk, splits, stream, before_dev);
+    if (pool_form == POOL_DEV)
+        return launch_split<POOL_DEV, true>(who, db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
+                                            workspace_bytes, 0, header_dev, capacity, n_qry, n_fields, topk, splits, stream, before_dev);
+    return launch_split<POOL_RING, true>(who, db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
+                                         workspace_bytes, 0, header_dev, capacity, n_qry, n_fields, topk, splits, stream, before_dev);
 }

@@ -171,6 +171,10 @@ _SIGNATURES = {
     "rat_pool_find": (c_int, [_P, c_int64, c_int64, c_int, c_int, _P, c_int64, c_int64, _P, c_int, _P, c_int64, _P, c_int64, _P, _P,
                               c_size_t, c_int, _P]),
     "rat_pool_set_labels": (c_int, [_P, c_int, _P, c_int64, c_int64, _P, _P, c_int64, c_int, _P]),
+    # a pool that looks at itself: live rows gathered with their horizons, and the scan with a horizon per query
+    "rat_pool_gather_rows": (c_int, [_P, _P, c_int, _P, c_int64, c_int64, _P, _P, _P, _P, c_int64, c_int, _P]),
+    "rat_bm25_topk_split_before": (c_int, [_P, c_int, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t, c_int64, c_int, c_int,
+                                           c_int, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

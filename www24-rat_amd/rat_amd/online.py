@@ -54,6 +54,17 @@ another row is the mapping's dtype rule, and ``rat_bm25_query_prepare_seg`` take
 first row, whose outputs are dropped — so 13 captured graphs serve every request mix of every total up to 4096 rows; ids and
 ``first_row`` live in static buffers refreshed before each replay.  ``score()`` and its graphs are untouched.
 
+The pool can look at itself.  A live row sent through ``score()`` finds ITSELF as its best neighbour, label attached, and every row
+that arrived after it besides.  ``score_rows(indices)`` / ``batch_rows(indices)`` / ``evaluate_rows(indices)`` take logical positions
+instead of ids: ``rat_pool_gather_rows`` copies the rows' ids and labels out of the row store and leaves every row's own position as
+its HORIZON, and ``rat_bm25_topk_split_before`` scans with that horizon per query — row i is scored against the rows older than it
+only, the way the reference's <X>-fold retrieval keeps a self-pool honest (``RetrievalIndex.retrieve(ids, before=...)`` is that scan
+for any ids and horizons).  A ``-1`` padding resolves to the newest row the query may see, ``max(i - 1, 0)``.  The IDF weights are
+those of the whole live pool as it stands, not of the pool as it was when the row arrived.  ``batch_rows`` carries the rows' real
+labels as ``y_true``, so it feeds ``model.train_step`` as well as the eval forward.  Nothing is read back in between, and with
+``graph=True`` the chain gather -> prepare -> scan -> assemble -> forward of a size is captured like a request's, in a dictionary of
+its own.
+
 Not served online (refused at construction): exact-match columns (numbering the groups needs a host ``np.unique`` over pool and
 queries), label-wise retrieval, topK > 32, more than 32 retrieval columns, data-parallel models.  Rows are deleted from a
 ``window=True`` pool only: the append-only form reserves its IDF tables for the rows that can still come, which deletions would undo.
@@ -188,6 +199,28 @@ def _row_list(indices, n, what):
     return np.ascontiguousarray(idx)
 
 
+_INT_DTYPES = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)
+
+
+def _before_list(before, B, device):
+    """what ``retrieve(ids, before=...)`` takes -> int64 [B] on the device.  A host array is validated — 1-D, integer dtype, B entries,
+    or ValueError — and uploaded; a device tensor is checked by shape and dtype only and passed through UNREAD (the kernel clamps)"""
+    if torch.is_tensor(before) and before.is_cuda:
+        if before.ndim != 1 or before.numel() != B:
+            raise ValueError("before must be a 1-D list of %d horizons (one per row), got shape %s" % (B, tuple(before.shape)))
+        if before.dtype not in _INT_DTYPES:
+            raise ValueError("before must be integers, got dtype %s" % before.dtype)
+        return before.detach().to(device, torch.int64).contiguous()
+    if torch.is_tensor(before):
+        before = before.detach().numpy()
+    b = np.asarray(before)
+    if b.ndim != 1 or b.size != B:
+        raise ValueError("before must be a 1-D list of %d horizons (one per row), got shape %s" % (B, tuple(b.shape)))
+    if not np.issubdtype(b.dtype, np.integer):
+        raise ValueError("before must be integers, got dtype %s" % b.dtype)
+    return torch.from_numpy(np.ascontiguousarray(b.astype(np.int64))).to(device, non_blocking=True)
+
+
 class RetrievalIndex:
     """A retrieval pool resident in HBM: its id columns field-major (what the top-K scan streams) and its per-column IDF tables
     (built once, on the host, by ``retrieval.idf_tables`` — numpy's float64 ``log``, so the weights are bit-identical to the offline
@@ -243,14 +276,22 @@ class RetrievalIndex:
         self.table_idf = up(np.concatenate([w for _, w in tables]).astype(np.float64))
         self.table_offsets = up(np.concatenate([[0], np.cumsum([len(v) for v, _ in tables])]).astype(np.int64))
 
-    def retrieve(self, ids, request_offsets=None, _first_row=None):
+    def retrieve(self, ids, request_offsets=None, _first_row=None, before=None):
         """ids [B, L] (full encoded rows) -> (values fp64 [B, K], indices int64 [B, K] with -1 padding, lens int64 [B]), on the device.
         With ``window=True`` the indices are LOGICAL positions (0 = the oldest live row, len(index) - 1 = the newest): they hold until
         the next eviction (an ``evict``, or an ``append`` into a full window) or ``delete``, which renumber the rows.
         ``request_offsets`` (int64 [R + 1], ascending from 0 to B; host or device): rows [off[r], off[r + 1]) are request r, and the
         result is the row-wise concatenation of ``retrieve(request_r)`` — one chain of launches for all of them.  Host-side offsets
         are validated (ValueError, nothing launched: not 1-D, not integer, not from 0 to B, not ascending, an empty request); device
-        offsets are used unread, without a synchronisation."""
+        offsets are used unread, without a synchronisation.
+        ``before`` (integers [B]; host or device): row q's candidates are the logical rows i < before[q] only — clamped to
+        [0, len(index)] on the device, so 0 or a negative value retrieves nothing and a value past the end sees the whole pool — and
+        the result equals, bit for bit, a retrieval of the same weights over a copy of the rows [0, before[q])
+        (``rat_bm25_topk_split_before``).  The weights are those of the WHOLE live pool.  A host array is validated (ValueError,
+        nothing launched: not 1-D, not integer, not B entries); a device tensor is used unread.  Not combined with
+        ``request_offsets`` (ValueError)."""
+        if before is not None and (request_offsets is not None or _first_row is not None):
+            raise ValueError("before cannot be combined with request_offsets: horizons inside request segments are not supported")
         ids = _as_device_ids(ids, self.device)
         if ids.shape[1] != self.row_len:
             raise ValueError("ids have %d columns, the pool's rows have %d" % (ids.shape[1], self.row_len))
@@ -258,8 +299,13 @@ class RetrievalIndex:
             raise ValueError("empty request")
         if request_offsets is not None:
             _first_row = _first_rows(*_request_offsets(request_offsets, ids.shape[0]), ids.shape[0], self.device)
+        if before is not None:
+            before = _before_list(before, ids.shape[0], self.device)
         qry_ids, qry_idf = ops.bm25_query_prepare(ids, self.cols, self.table_ids, self.table_idf, self.table_offsets,
                                                   first_row=_first_row, lib=self._lib)
+        if before is not None:
+            return ops.bm25_topk_split_before(self.db_t, qry_ids, qry_idf, before, self.topK, splits=self.splits, lib=self._lib,
+                                              **self._pool_form())
         if self.window:
             return ops.bm25_topk_split_ring(self.db_t, self.count, qry_ids, qry_idf, self.topK, splits=self.splits, lib=self._lib)
         if self.capacity is not None:
@@ -494,6 +540,25 @@ class _RequestGraph:
         return self.y_pred.clone()
 
 
+class _RowsGraph:
+    """gather -> prepare -> horizon scan -> assemble -> eval forward of one number of pool rows as one linear hipGraph; the logical
+    indices are the static input"""
+
+    def __init__(self, scorer, indices):
+        self.static_idx = indices.clone()
+        self._stream = torch.cuda.Stream(device=indices.device)
+        self.graph = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        with torch.no_grad(), torch.cuda.graph(self.graph, stream=self._stream, capture_error_mode="thread_local"):
+            self.y_pred = scorer._score_rows_eager(self.static_idx)
+
+    def run(self, indices):
+        if indices.data_ptr() != self.static_idx.data_ptr():
+            self.static_idx.copy_(indices, non_blocking=True)
+        self.graph.replay()
+        return self.y_pred.clone()
+
+
 class _BucketGraph:
     """the same chain for P rows (a power of two) that hold ANY mix of requests: ids and first_row are static inputs, refreshed before
     each replay; linear on one stream like _RequestGraph"""
@@ -564,6 +629,7 @@ class OnlineScorer:
         self._consts = {}              # request size -> (rows = arange(B), labels = zeros(B))
         self._graphs = {}              # key -> [eager requests seen, _RequestGraph | False | None]
         self._bucket_graphs = {}       # score_requests: (bucket, ...) -> [eager calls seen, _BucketGraph | False | None]
+        self._rows_graphs = {}         # score_rows: key -> [eager calls seen, _RowsGraph | False | None]
         self._found = None             # relabel_where's index list (one entry per row the pool can hold), from its first call on
 
     # ------------------------------------------------------------------------------------------------------------------
@@ -684,6 +750,95 @@ class OnlineScorer:
         with torch.no_grad():
             g = self._graph_for(ids)
             return g.run(ids) if g is not None else self._score_eager(ids)
+
+    # ---- the pool looks at itself ------------------------------------------------------------------------------------------
+    def _row_indices(self, indices, what):
+        """logical row indices -> int64 [B] on the device.  Host-side ones are validated as ``set_labels`` validates them (ValueError:
+        a non-integer dtype, an index outside [0, len(pool)), a duplicate, not 1-D) and an empty list is refused; a DEVICE tensor is
+        checked by shape and dtype and passed through unread — the gather answers an index outside the live rows with a row of zeros"""
+        if torch.is_tensor(indices) and indices.is_cuda:
+            if indices.ndim != 1:
+                raise ValueError("%s takes a 1-D list of logical row indices, got shape %s" % (what, tuple(indices.shape)))
+            if indices.dtype not in _INT_DTYPES:
+                raise ValueError("%s takes integer row indices, got dtype %s" % (what, indices.dtype))
+            idx = indices.detach().to(self.device, torch.int64).contiguous()
+        else:
+            idx = torch.from_numpy(_row_list(indices, len(self.index), what)).to(self.device)
+        if idx.numel() == 0:
+            raise ValueError("%s: empty list of rows" % what)
+        return idx
+
+    def _assemble_rows(self, idx):
+        """idx int64 [B] (device) -> (idx, label_ids, y_true) of the rows at those logical positions, each with the neighbours it had
+        when it arrived: horizon = its own position.  Nothing is read back between the launches."""
+        form = self.index._pool_form()
+        ids, labels, before = ops.pool_gather_rows(self.pool_ids, self.pool_labels, idx, lib=self._lib, **form)
+        _values, nbr, _lens = self.index.retrieve(ids, before=before)
+        # a -1 padding is the newest row the query may see, not the pool's newest row (which the assembly would take for it)
+        nbr = torch.where(nbr < 0, (before - 1).clamp_(min=0).unsqueeze(1), nbr)
+        rows, _zeros = self._constants(idx.numel())
+        if self.index.window:
+            return ops.batch_assemble_ring(ids, labels, self.pool_ids, self.pool_labels, nbr, rows, self.index.count, lib=self._lib)
+        if self.index.capacity is not None:
+            return ops.batch_assemble_dev(ids, labels, self.pool_ids, self.pool_labels, nbr, rows, self.index.count, lib=self._lib)
+        return ops.batch_assemble(ids, labels, self.pool_ids, self.pool_labels, nbr, rows, lib=self._lib)
+
+    def _score_rows_eager(self, idx):
+        y_pred, _loss, _reg, _saved = self.model._run_forward(self._assemble_rows(idx), save=False, with_reg=False)
+        return y_pred.reshape(-1)
+
+    def batch_rows(self, indices):
+        """-> data.DeviceBatch of the live rows at the logical positions ``indices``: ``idx[:, 0]`` their ids, ``y_true`` their REAL
+        labels (the batch can go straight into ``model.train_step``), and as neighbours of row i only rows OLDER than i — the scan
+        runs with the row's own position as its horizon, so the row never retrieves itself or anything that arrived after it.  A
+        ``-1`` padding resolves to row ``max(i - 1, 0)``, the newest row i may see (row 0, which has nobody before it, pads with
+        itself).  The IDF weights are those of the whole live pool as it stands."""
+        return DeviceBatch(*self._assemble_rows(self._row_indices(indices, "batch_rows")))
+
+    def score_rows(self, indices):
+        """fp32 [B] predictions for the live rows at ``indices``, each scored against the rows older than it (``batch_rows``).  With
+        ``graph=True`` and device indices, the chain of a size (<= ``graph_max_batch``) is captured after ``graph_warmup`` eager calls
+        and replayed with the indices as its static input; it reads the header, the labels and the weights at replay time."""
+        if self.model.training:
+            raise RuntimeError("OnlineScorer.score_rows needs the model in eval mode (model.eval())")
+        given_on_device = torch.is_tensor(indices) and indices.is_cuda
+        idx = self._row_indices(indices, "score_rows")
+        with torch.no_grad():
+            g = self._rows_graph_for(idx) if given_on_device else None
+            return g.run(idx) if g is not None else self._score_rows_eager(idx)
+
+    def evaluate_rows(self, indices):
+        """{"logloss": ..., "AUC": ...} of ``score_rows(indices)`` against the rows' stored labels (``metrics.evaluate_metrics`` on the
+        host, after one device-to-host copy of predictions and labels): how well the model does on the traffic in the window"""
+        from .metrics import evaluate_metrics
+        idx = self._row_indices(indices, "evaluate_rows")
+        y_pred = self.score_rows(idx)
+        _ids, labels, _before = ops.pool_gather_rows(self.pool_ids, self.pool_labels, idx, lib=self._lib, **self.index._pool_form())
+        both = torch.stack([y_pred, labels]).cpu().numpy()
+        return evaluate_metrics(both[1].astype(np.float64), both[0].astype(np.float64), ["logloss", "AUC"])
+
+    def _rows_graph_for(self, idx):
+        B = idx.numel()
+        if not (self.graph and idx.is_cuda and B <= self.graph_max_batch):
+            return None
+        key = (B, self.model._eval_graph_key((B, self.index.topK + 1, self.index.row_len)))
+        entry = self._rows_graphs.get(key)
+        if entry is None:
+            if len(self._rows_graphs) >= self.graph_sizes:
+                return None
+            entry = self._rows_graphs[key] = [0, None]
+        if entry[1] is None:
+            entry[0] += 1
+            if entry[0] <= self.graph_warmup:
+                return None
+            try:
+                entry[1] = _RowsGraph(self, idx)
+            except Exception as exc:
+                import logging
+                logging.warning("hipGraph capture of the pool-row scoring failed (%s: %s); continuing with eager launches",
+                                type(exc).__name__, exc)
+                entry[1] = False
+        return entry[1] or None
 
     # ---- requests that share a launch ------------------------------------------------------------------------------------
     def _requests(self, requests):

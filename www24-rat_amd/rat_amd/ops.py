@@ -1161,3 +1161,46 @@ def batch_assemble_ring(data_ids, data_labels, pool_ids, pool_labels, retr_indic
     lib.call("rat_batch_assemble_ring", _p(data_ids), _p(data_labels), _p(pool_ids), _p(pool_labels), _p(retr_indices), _p(rows),
              _p(idx), _p(label_ids), _p(y_true), Q, _p(header), int(pool_ids.shape[0]), B, K, L, _stream(data_ids))
     return idx, label_ids, y_true
+
+
+# ----------------------------------------------------------------------------- a pool that looks at itself (rat_amd/online.py)
+def pool_gather_rows(pool_ids, pool_labels, indices, header=None, ring=False, n_rows=None, lib=None):
+    """-> (ids int32 [B, L], labels fp32 [B], before int64 [B]), on the device: the logical rows `indices` (int64 [B], device) of
+    pool_ids int32 [capacity, L] / pool_labels fp32 [capacity]; an index < 0 or >= the live row count gives a row of zeros, label 0.
+    before = the indices clamped to [0, live row count] — every row's horizon for bm25_topk_split_before.  The pool's form as in
+    _pool_form."""
+    lib = lib or get_lib()
+    _chk(pool_ids, torch.int32, "pool_ids"), _chk(pool_labels, name="pool_labels"), _chk(indices, torch.int64, "indices")
+    capacity, L = pool_ids.shape
+    B = indices.numel()
+    assert indices.ndim == 1 and pool_labels.numel() == capacity
+    form, n_rows = _pool_form(header, ring, n_rows, capacity)
+    dev = pool_ids.device
+    out_ids = torch.empty((B, L), dtype=torch.int32, device=dev)
+    out_labels = torch.empty((B,), dtype=torch.float32, device=dev)
+    out_before = torch.empty((B,), dtype=torch.int64, device=dev)
+    lib.call("rat_pool_gather_rows", _p(pool_ids), _p(pool_labels), form, _p(header), n_rows, capacity, _p(indices), _p(out_ids),
+             _p(out_labels), _p(out_before), B, L, _stream(pool_ids))
+    return out_ids, out_labels, out_before
+
+
+def bm25_topk_split_before(db_t, qry_ids, qry_idf, before, topk, header=None, ring=False, n_rows=None, splits=0, lib=None):
+    """bm25_topk_split with a horizon per query: query q sees the logical rows i < before[q] (int64 [Q], device; clamped to
+    [0, live row count] on the device) of db_t int32 [F, capacity].  The pool's form as in _pool_form; splits = 0: chosen from the
+    capacity"""
+    lib = lib or get_lib()
+    _chk(db_t, torch.int32, "db_t"), _chk(qry_ids, torch.int32, "qry_ids"), _chk(qry_idf, torch.float64, "qry_idf")
+    _chk(before, torch.int64, "before")
+    F, capacity = db_t.shape
+    Q = qry_ids.shape[0]
+    assert tuple(qry_ids.shape) == (Q, F) and tuple(qry_idf.shape) == (Q, F) and before.ndim == 1 and before.numel() == Q
+    form, n_rows = _pool_form(header, ring, n_rows, capacity)
+    dev = db_t.device
+    nbytes = lib.size("rat_bm25_topk_split_workspace", Q, int(topk), int(splits))
+    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    out_v = torch.empty((Q, topk), dtype=torch.float64, device=dev)
+    out_i = torch.empty((Q, topk), dtype=torch.int64, device=dev)
+    out_l = torch.empty((Q,), dtype=torch.int64, device=dev)
+    lib.call("rat_bm25_topk_split_before", _p(db_t), form, _p(header), n_rows, capacity, _p(qry_ids), _p(qry_idf), _p(before), _p(out_v),
+             _p(out_i), _p(out_l), _p(ws), ws.numel() * 8, Q, F, int(topk), int(splits), _stream(db_t))
+    return out_v, out_i, out_l
