@@ -685,7 +685,10 @@ int rat_clip_adam(float* w, const float* g, float* m, float* v, int64_t n, const
  * rat_adam_tick      : the optimizer's clock on the device: *step_dev += 1, hyper_out[0..2] = {lr/(1-beta1^t), 1/sqrt(1-beta2^t),
  *                      lr} from *lr_dev (double arithmetic like torch.optim.Adam's host code) — a replayed graph needs no new
  *                      kernel arguments.
- * rat_adam_rows_dev  : rat_adam_rows with the two step scalars read from hyper_dev. */
+ * rat_adam_rows_dev  : rat_adam_rows with the two step scalars read from hyper_dev.
+ * Every optimizer entry point takes beta1 / beta2 / alpha (p0) as floats and forms 1 - beta and beta^t in double from the double
+ * with the float's shortest round-trip decimal (0.999f -> 0.999), as torch.optim forms them from its Python floats: 1 - 0.999f is
+ * 1.3e-5 (relative) off 0.001. */
 int rat_adam_tick(int32_t* step_dev, const float* lr_dev, float beta1, float beta2, float* hyper_out, void* stream);
 /* ABI v7 — what a fused training iteration starts with, in one launch: rat_adam_tick, scalars[0 .. nscalars) = 0 (the step's
  * accumulators: BCE sum, clip norm^2, regulariser value) and counters[i] += 1 for i < ncounters (nn.BatchNorm1d.num_batches_tracked of

@@ -75,7 +75,8 @@ sumsq_kernel(const float* __restrict__ g, int64_t n, float* out) {
 //   kind 2 Adagrad  s += g g ;            w -= lr g / (sqrt(s) + eps)
 //   kind 3 RMSprop  s = alpha s + ((1 - alpha) g) g ;  w -= lr g / (sqrt(s) + eps)
 // (kind 0 = Adam keeps its own code below.)  `v` is the one state buffer these use; `m` is untouched.
-__device__ __forceinline__ void opt_other1(int kind, float& w, float gv, float& s, float lr, float p0, float eps) {
+// omp0 = 1 - alpha, formed in double on the host (rat_decimal) like omb1 / omb2 of the Adam kernels.
+__device__ __forceinline__ void opt_other1(int kind, float& w, float gv, float& s, float lr, float p0, float omp0, float eps) {
     if (kind == 1) {
         w -= lr * gv;
     } else if (kind == 2) {
@@ -83,14 +84,14 @@ __device__ __forceinline__ void opt_other1(int kind, float& w, float gv, float& 
         w -= lr * gv / (sqrtf(s) + eps);
     } else {
         s = p0 * s;
-        s = s + (1.0f - p0) * gv * gv;
+        s = s + omp0 * gv * gv;
         w -= lr * gv / (sqrtf(s) + eps);
     }
 }
 
 __global__ void __launch_bounds__(OPT_THREADS)
 clip_other_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ v, int64_t n, const float* norm_sq,
-                  float max_norm, float lr, int kind, float p0, float eps) {
+                  float max_norm, float lr, int kind, float p0, float omp0, float eps) {
     float coef = 1.0f;
     if (norm_sq != nullptr) {
         coef = max_norm / (sqrtf(*norm_sq) + 1e-6f);
@@ -98,7 +99,7 @@ clip_other_kernel(float* __restrict__ w, const float* __restrict__ g, float* __r
     }
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float wv = w[i], sv = kind == 1 ? 0.f : v[i];
-        opt_other1(kind, wv, g[i] * coef, sv, lr, p0, eps);
+        opt_other1(kind, wv, g[i] * coef, sv, lr, p0, omp0, eps);
         w[i] = wv;
         if (kind != 1) v[i] = sv;
     }
@@ -106,7 +107,7 @@ clip_other_kernel(float* __restrict__ w, const float* __restrict__ g, float* __r
 
 __global__ void __launch_bounds__(OPT_THREADS)
 clip_adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
-                 const float* norm_sq, float max_norm, float step_size, float beta1, float beta2, float eps,
+                 const float* norm_sq, float max_norm, float step_size, float beta1, float omb1, float beta2, float omb2, float eps,
                  float inv_sqrt_bc2) {
     float coef = 1.0f;
     if (norm_sq != nullptr) {
@@ -115,8 +116,8 @@ clip_adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __re
     }
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float gv = g[i] * coef;
-        const float mv = beta1 * m[i] + (1.0f - beta1) * gv;
-        const float vv = beta2 * v[i] + (1.0f - beta2) * gv * gv;
+        const float mv = beta1 * m[i] + omb1 * gv;
+        const float vv = beta2 * v[i] + omb2 * gv * gv;
         m[i] = mv;
         v[i] = vv;
         const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
@@ -212,11 +213,12 @@ sumsq_reg_kernel(const float* __restrict__ g, const float* __restrict__ w, int64
     }
 }
 
+// omb1 = 1 - beta1, omb2 = 1 - beta2: formed in double on the host from the betas' decimal values (rat_decimal), as torch.optim forms them
 __device__ __forceinline__ float opt_adam1(float& w, float g, float& m, float& v, float lam, float coef, float step_size, float beta1,
-                                           float beta2, float eps, float inv_sqrt_bc2) {
+                                           float omb1, float beta2, float omb2, float eps, float inv_sqrt_bc2) {
     const float gv = fmaf(lam, w, g) * coef;
-    m = beta1 * m + (1.0f - beta1) * gv;
-    v = beta2 * v + (1.0f - beta2) * gv * gv;
+    m = beta1 * m + omb1 * gv;
+    v = beta2 * v + omb2 * gv * gv;
     w -= step_size * m / (sqrtf(v) * inv_sqrt_bc2 + eps);
     return 0.f;
 }
@@ -224,7 +226,8 @@ __device__ __forceinline__ float opt_adam1(float& w, float g, float& m, float& v
 __global__ void __launch_bounds__(OPT_THREADS)
 clip_adam_fused_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
                        int64_t n_split, float lam_a, float lam_b, const float* lam_scale_dev, const float* norm_sq, float max_norm,
-                       const float* __restrict__ hyper, float beta1, float beta2, float eps, int zero_g, int vec, int kind) {
+                       const float* __restrict__ hyper, float beta1, float omb1, float beta2, float omb2, float eps, int zero_g, int vec,
+                       int kind) {
     float coef = 1.0f;
     if (norm_sq != nullptr) {
         coef = max_norm / (sqrtf(*norm_sq) + 1e-6f);
@@ -239,7 +242,7 @@ clip_adam_fused_kernel(float* __restrict__ w, float* __restrict__ g, float* __re
         const float lr = hyper[2];
         for (int64_t i = tid; i < n; i += nthr) {
             float wv = w[i], sv = kind == 1 ? 0.f : v[i];
-            opt_other1(kind, wv, fmaf(i < n_split ? la : lb, wv, g[i]) * coef, sv, lr, beta1, eps);
+            opt_other1(kind, wv, fmaf(i < n_split ? la : lb, wv, g[i]) * coef, sv, lr, beta1, omb1, eps);
             w[i] = wv;
             if (kind != 1) v[i] = sv;
             if (zero_g) g[i] = 0.f;
@@ -250,10 +253,10 @@ clip_adam_fused_kernel(float* __restrict__ w, float* __restrict__ g, float* __re
         const int64_t n4 = n >> 2, s4 = n_split >> 2;
         auto one = [&](int64_t i, float4 wv, float4 mv, float4 vv, const float4& gv) {
             const float l = i < s4 ? la : lb;
-            opt_adam1(wv.x, gv.x, mv.x, vv.x, l, coef, step_size, beta1, beta2, eps, inv_sqrt_bc2);
-            opt_adam1(wv.y, gv.y, mv.y, vv.y, l, coef, step_size, beta1, beta2, eps, inv_sqrt_bc2);
-            opt_adam1(wv.z, gv.z, mv.z, vv.z, l, coef, step_size, beta1, beta2, eps, inv_sqrt_bc2);
-            opt_adam1(wv.w, gv.w, mv.w, vv.w, l, coef, step_size, beta1, beta2, eps, inv_sqrt_bc2);
+            opt_adam1(wv.x, gv.x, mv.x, vv.x, l, coef, step_size, beta1, omb1, beta2, omb2, eps, inv_sqrt_bc2);
+            opt_adam1(wv.y, gv.y, mv.y, vv.y, l, coef, step_size, beta1, omb1, beta2, omb2, eps, inv_sqrt_bc2);
+            opt_adam1(wv.z, gv.z, mv.z, vv.z, l, coef, step_size, beta1, omb1, beta2, omb2, eps, inv_sqrt_bc2);
+            opt_adam1(wv.w, gv.w, mv.w, vv.w, l, coef, step_size, beta1, omb1, beta2, omb2, eps, inv_sqrt_bc2);
             opt_st4(w, i, wv); opt_st4_stream(m, i, mv); opt_st4_stream(v, i, vv);
             if (zero_g) opt_st4_stream(g, i, make_float4(0.f, 0.f, 0.f, 0.f));
         };
@@ -275,7 +278,7 @@ clip_adam_fused_kernel(float* __restrict__ w, float* __restrict__ g, float* __re
     }
     for (int64_t i = head + tid; i < n; i += nthr) {
         float wv = w[i], mv = m[i], vv = v[i];
-        opt_adam1(wv, g[i], mv, vv, i < n_split ? la : lb, coef, step_size, beta1, beta2, eps, inv_sqrt_bc2);
+        opt_adam1(wv, g[i], mv, vv, i < n_split ? la : lb, coef, step_size, beta1, omb1, beta2, omb2, eps, inv_sqrt_bc2);
         w[i] = wv; m[i] = mv; v[i] = vv;
         if (zero_g) g[i] = 0.f;
     }
@@ -283,13 +286,13 @@ clip_adam_fused_kernel(float* __restrict__ w, float* __restrict__ g, float* __re
 
 // the optimizer's clock on the device (so that a captured step — a hipGraph replay — needs no new kernel arguments):
 // *step += 1; hyper[0] = lr / (1 - beta1^step), hyper[1] = 1 / sqrt(1 - beta2^step), hyper[2] = lr   (torch.optim.Adam's
-// bias corrections, evaluated in double like the host does)
-__global__ void adam_tick_kernel(int32_t* step, const float* lr, float beta1, float beta2, float* hyper) {
+// bias corrections, evaluated in double like the host does, from the betas the host widened with rat_decimal)
+__global__ void adam_tick_kernel(int32_t* step, const float* lr, double beta1, double beta2, float* hyper) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const int s = *step + 1;
     *step = s;
-    const double bc1 = 1.0 - pow((double)beta1, (double)s);
-    const double bc2 = 1.0 - pow((double)beta2, (double)s);
+    const double bc1 = 1.0 - pow(beta1, (double)s);
+    const double bc2 = 1.0 - pow(beta2, (double)s);
     hyper[0] = (float)((double)*lr / bc1);
     hyper[1] = (float)(1.0 / sqrt(bc2));
     hyper[2] = *lr;
@@ -297,7 +300,7 @@ __global__ void adam_tick_kernel(int32_t* step, const float* lr, float beta1, fl
 
 // the bookkeeping a training iteration starts with, in ONE launch: the clock tick above, the step's accumulator scalars cleared
 // (BCE sum | clip norm^2 | regulariser value | spare) and every BatchNorm layer's num_batches_tracked advanced
-__global__ void step_begin_kernel(int32_t* step, const float* lr, float beta1, float beta2, float* hyper, float* scalars, int nscalars,
+__global__ void step_begin_kernel(int32_t* step, const float* lr, double beta1, double beta2, float* hyper, float* scalars, int nscalars,
                                   int64_t* counters, int ncounters) {
     if (blockIdx.x != 0) return;
     for (int i = threadIdx.x; i < nscalars; i += blockDim.x) scalars[i] = 0.f;
@@ -305,8 +308,8 @@ __global__ void step_begin_kernel(int32_t* step, const float* lr, float beta1, f
     if (threadIdx.x != 0) return;
     const int s = *step + 1;
     *step = s;
-    const double bc1 = 1.0 - pow((double)beta1, (double)s);
-    const double bc2 = 1.0 - pow((double)beta2, (double)s);
+    const double bc1 = 1.0 - pow(beta1, (double)s);
+    const double bc2 = 1.0 - pow(beta2, (double)s);
     hyper[0] = (float)((double)*lr / bc1);
     hyper[1] = (float)(1.0 / sqrt(bc2));
     hyper[2] = *lr;
@@ -348,10 +351,11 @@ extern "C" int rat_sumsq(const float* g, int64_t n, float* norm_sq_out, void* st
 extern "C" int rat_clip_adam(float* w, const float* g, float* m, float* v, int64_t n, const float* norm_sq, float max_norm,
                              float lr, float beta1, float beta2, float eps, int step, void* stream) {
     RAT_REQUIRE(n > 0 && w && g && m && v && step >= 1, "bad args");
-    const double bc1 = 1.0 - pow((double)beta1, step);
-    const double bc2 = 1.0 - pow((double)beta2, step);
+    const double b1 = rat_decimal(beta1), b2 = rat_decimal(beta2);
+    const double bc1 = 1.0 - pow(b1, step);
+    const double bc2 = 1.0 - pow(b2, step);
     RAT_LAUNCH(clip_adam_kernel, opt_blocks(n), OPT_THREADS, 0, stream, w, g, m, v, n, norm_sq, max_norm,
-               (float)(lr / bc1), beta1, beta2, eps, (float)(1.0 / sqrt(bc2)));
+               (float)(lr / bc1), beta1, (float)(1.0 - b1), beta2, (float)(1.0 - b2), eps, (float)(1.0 / sqrt(bc2)));
     return rat_check_launch("rat_clip_adam");
 }
 
@@ -363,7 +367,7 @@ static bool opt_vec_ok(std::initializer_list<const void*> ps, int64_t n_split) {
 
 extern "C" int rat_adam_tick(int32_t* step_dev, const float* lr_dev, float beta1, float beta2, float* hyper_out, void* stream) {
     RAT_REQUIRE(step_dev && lr_dev && hyper_out, "bad args");
-    RAT_LAUNCH(adam_tick_kernel, 1, 64, 0, stream, step_dev, lr_dev, beta1, beta2, hyper_out);
+    RAT_LAUNCH(adam_tick_kernel, 1, 64, 0, stream, step_dev, lr_dev, rat_decimal(beta1), rat_decimal(beta2), hyper_out);
     return rat_check_launch("rat_adam_tick");
 }
 
@@ -371,7 +375,8 @@ extern "C" int rat_step_begin(int32_t* step_dev, const float* lr_dev, float beta
                               int nscalars, int64_t* counters, int ncounters, void* stream) {
     RAT_REQUIRE(step_dev && lr_dev && hyper_out && nscalars >= 0 && ncounters >= 0 && (scalars || nscalars == 0) && (counters || ncounters == 0),
                 "bad args");
-    RAT_LAUNCH(step_begin_kernel, 1, 64, 0, stream, step_dev, lr_dev, beta1, beta2, hyper_out, scalars, nscalars, counters, ncounters);
+    RAT_LAUNCH(step_begin_kernel, 1, 64, 0, stream, step_dev, lr_dev, rat_decimal(beta1), rat_decimal(beta2), hyper_out, scalars, nscalars,
+               counters, ncounters);
     return rat_check_launch("rat_step_begin");
 }
 
@@ -390,7 +395,8 @@ extern "C" int rat_clip_adam_fused(float* w, float* g, float* m, float* v, int64
     RAT_REQUIRE(n > 0 && w && g && m && v && hyper_dev && n_split >= 0 && n_split <= n, "bad args");
     const int vec = opt_vec_ok({w, g, m, v}, n_split) ? 1 : 0;
     RAT_LAUNCH(clip_adam_fused_kernel, opt_blocks(n), OPT_THREADS, 0, stream, w, g, m, v, n, n_split, lam_a, lam_b, lam_scale_dev,
-               norm_sq, max_norm, hyper_dev, beta1, beta2, eps, zero_g, vec, 0);
+               norm_sq, max_norm, hyper_dev, beta1, (float)(1.0 - rat_decimal(beta1)), beta2, (float)(1.0 - rat_decimal(beta2)), eps, zero_g,
+               vec, 0);
     return rat_check_launch("rat_clip_adam_fused");
 }
 
@@ -399,14 +405,15 @@ extern "C" int rat_clip_opt_fused(float* w, float* g, float* state, int64_t n, i
                                   float p0, float eps, int zero_g, void* stream) {
     RAT_REQUIRE(n > 0 && w && g && hyper_dev && n_split >= 0 && n_split <= n && kind >= 1 && kind <= 3 && (kind == 1 || state), "bad args");
     RAT_LAUNCH(clip_adam_fused_kernel, opt_blocks(n), OPT_THREADS, 0, stream, w, g, (float*)nullptr, state, n, n_split, lam_a, lam_b,
-               lam_scale_dev, norm_sq, max_norm, hyper_dev, p0, 0.f, eps, zero_g, 0, kind);
+               lam_scale_dev, norm_sq, max_norm, hyper_dev, p0, (float)(1.0 - rat_decimal(p0)), 0.f, 1.f, eps, zero_g, 0, kind);
     return rat_check_launch("rat_clip_opt_fused");
 }
 
 extern "C" int rat_clip_opt(float* w, const float* g, float* state, int64_t n, const float* norm_sq, float max_norm, float lr, int kind,
                             float p0, float eps, void* stream) {
     RAT_REQUIRE(n > 0 && w && g && kind >= 1 && kind <= 3 && (kind == 1 || state), "bad args");
-    RAT_LAUNCH(clip_other_kernel, opt_blocks(n), OPT_THREADS, 0, stream, w, g, state, n, norm_sq, max_norm, lr, kind, p0, eps);
+    RAT_LAUNCH(clip_other_kernel, opt_blocks(n), OPT_THREADS, 0, stream, w, g, state, n, norm_sq, max_norm, lr, kind, p0,
+               (float)(1.0 - rat_decimal(p0)), eps);
     return rat_check_launch("rat_clip_opt");
 }
 

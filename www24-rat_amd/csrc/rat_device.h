@@ -12,6 +12,8 @@
 
 #include <stdint.h>
 #include <stddef.h>
+#include <stdio.h>
+#include <stdlib.h>
 
 #ifdef RAT_EMU
 #include "hip_emu.h"
@@ -70,6 +72,18 @@ int rat_max_blocks();                                 // 256 (one work-group per
     } while (0)
 
 static inline int rat_round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// A hyper-parameter that crossed the C ABI as a float, widened to the double with the float's SHORTEST round-trip decimal: 0.999f -> 0.999
+// (a plain cast gives 0.99900001287...).  torch.optim holds beta / alpha in double and forms 1 - beta and beta^t there before it rounds
+// to the tensors' type; formed from the float, 1 - 0.999f is 1.3e-5 (relative) off 0.001 — and with it every term Adam adds to v.
+static inline double rat_decimal(float x) {
+    char buf[40];
+    for (int digits = 1; digits <= 9; ++digits) {
+        snprintf(buf, sizeof(buf), "%.*g", digits, (double)x);
+        if (strtof(buf, nullptr) == x) return strtod(buf, nullptr);
+    }
+    return (double)x;
+}
 
 // ------------------------------------------------------------------------------------------- device side
 #define RAT_WAVE 64

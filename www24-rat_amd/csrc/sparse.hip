@@ -327,7 +327,7 @@ sumsq_rows_kernel(const float* __restrict__ g, const int32_t* __restrict__ count
 __global__ void __launch_bounds__(SP_THREADS)
 adam_rows_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v, const int32_t* __restrict__ rows,
                  const float* __restrict__ g, const int32_t* __restrict__ count, int d, const float* norm_sq, float max_norm,
-                 float step_size, float beta1, float beta2, float eps, float inv_sqrt_bc2) {
+                 float step_size, float beta1, float omb1, float beta2, float omb2, float eps, float inv_sqrt_bc2) {
     float coef = 1.0f;
     if (norm_sq != nullptr) {
         coef = max_norm / (sqrtf(*norm_sq) + 1e-6f);
@@ -338,8 +338,8 @@ adam_rows_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict
         const int64_t s = i / d;
         const int64_t o = (int64_t)rows[s] * d + (i - s * d);
         const float gv = g[i] * coef;
-        const float mv = beta1 * m[o] + (1.0f - beta1) * gv;
-        const float vv = beta2 * v[o] + (1.0f - beta2) * gv * gv;
+        const float mv = beta1 * m[o] + omb1 * gv;
+        const float vv = beta2 * v[o] + omb2 * gv * gv;
         m[o] = mv;
         v[o] = vv;
         w[o] -= step_size * mv / (sqrtf(vv) * inv_sqrt_bc2 + eps);
@@ -350,7 +350,7 @@ adam_rows_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict
 __global__ void __launch_bounds__(SP_THREADS)
 adam_rows_dev_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v, const int32_t* __restrict__ rows,
                      const float* __restrict__ g, const int32_t* __restrict__ count, int d, const float* norm_sq, float max_norm,
-                     const float* __restrict__ hyper, float beta1, float beta2, float eps) {
+                     const float* __restrict__ hyper, float beta1, float omb1, float beta2, float omb2, float eps) {
     float coef = 1.0f;
     if (norm_sq != nullptr) {
         coef = max_norm / (sqrtf(*norm_sq) + 1e-6f);
@@ -362,8 +362,8 @@ adam_rows_dev_kernel(float* __restrict__ w, float* __restrict__ m, float* __rest
         const int64_t s = i / d;
         const int64_t o = (int64_t)rows[s] * d + (i - s * d);
         const float gv = g[i] * coef;
-        const float mv = beta1 * m[o] + (1.0f - beta1) * gv;
-        const float vv = beta2 * v[o] + (1.0f - beta2) * gv * gv;
+        const float mv = beta1 * m[o] + omb1 * gv;
+        const float vv = beta2 * v[o] + omb2 * gv * gv;
         m[o] = mv;
         v[o] = vv;
         w[o] -= step_size * mv / (sqrtf(vv) * inv_sqrt_bc2 + eps);
@@ -622,12 +622,13 @@ extern "C" int rat_adam_rows(float* w_base, float* m_base, float* v_base, const 
                              const int32_t* count_dev, int64_t max_rows, int d, const float* norm_sq, float max_norm, float lr,
                              float beta1, float beta2, float eps, int step, void* stream) {
     RAT_REQUIRE(w_base && m_base && v_base && rows && grads && count_dev && d > 0 && max_rows > 0 && step >= 1, "bad args");
-    const double bc1 = 1.0 - pow((double)beta1, step);
-    const double bc2 = 1.0 - pow((double)beta2, step);
+    const double b1 = rat_decimal(beta1), b2 = rat_decimal(beta2);         // 1 - beta and beta^t from the decimal values, as torch.optim forms them
+    const double bc1 = 1.0 - pow(b1, step);
+    const double bc2 = 1.0 - pow(b2, step);
     int64_t blocks = (max_rows * d + SP_THREADS * 4 - 1) / (SP_THREADS * 4);
     blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
     RAT_LAUNCH(adam_rows_kernel, (unsigned)blocks, SP_THREADS, 0, stream, w_base, m_base, v_base, rows, grads, count_dev, d, norm_sq,
-               max_norm, (float)(lr / bc1), beta1, beta2, eps, (float)(1.0 / sqrt(bc2)));
+               max_norm, (float)(lr / bc1), beta1, (float)(1.0 - b1), beta2, (float)(1.0 - b2), eps, (float)(1.0 / sqrt(bc2)));
     return rat_check_launch("rat_adam_rows");
 }
 
@@ -638,7 +639,7 @@ extern "C" int rat_adam_rows_dev(float* w_base, float* m_base, float* v_base, co
     int64_t blocks = (max_rows * d + SP_THREADS * 4 - 1) / (SP_THREADS * 4);
     blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
     RAT_LAUNCH(adam_rows_dev_kernel, (unsigned)blocks, SP_THREADS, 0, stream, w_base, m_base, v_base, rows, grads, count_dev, d, norm_sq,
-               max_norm, hyper_dev, beta1, beta2, eps);
+               max_norm, hyper_dev, beta1, (float)(1.0 - rat_decimal(beta1)), beta2, (float)(1.0 - rat_decimal(beta2)), eps);
     return rat_check_launch("rat_adam_rows_dev");
 }
 

@@ -806,10 +806,11 @@ def clip_opt(w, g, state, norm_sq, max_norm, lr, kind, p0, eps, lib=None):
              _stream(w))
 
 
-def clip_opt_fused(w, g, state, n_split, lam_a, lam_b, norm_sq, max_norm, hyper, kind, p0, eps, zero_g=True, lib=None):
+def clip_opt_fused(w, g, state, n_split, lam_a, lam_b, norm_sq, max_norm, hyper, kind, p0, eps, zero_g=True, lam_scale_dev=None,
+                   lib=None):
     lib = lib or get_lib()
-    lib.call("rat_clip_opt_fused", _p(w), _p(g), _p(state), w.numel(), int(n_split), float(lam_a), float(lam_b), None, _p(norm_sq),
-             float(max_norm), _p(hyper), int(kind), float(p0), float(eps), int(bool(zero_g)), _stream(w))
+    lib.call("rat_clip_opt_fused", _p(w), _p(g), _p(state), w.numel(), int(n_split), float(lam_a), float(lam_b), _p(lam_scale_dev),
+             _p(norm_sq), float(max_norm), _p(hyper), int(kind), float(p0), float(eps), int(bool(zero_g)), _stream(w))
 
 
 def dropout(x, p, seed, out=None, lib=None):
