@@ -491,6 +491,50 @@ int rat_bm25_topk_split_before(const int32_t* db_ids_field_major, int pool_form,
                                double* out_values, int64_t* out_indices, int64_t* out_lens, void* workspace, size_t workspace_bytes,
                                int64_t n_qry, int n_fields, int topk, int splits, void* stream);
 
+/* Neighbours restricted to rows equal on given columns (additive in ABI v9 as well): the reference's exact_match_col_indices
+ * (fuxictr/datasets/data_utils.py:851-866, 895-938) on the request path, with no group numbers — db_ids_field_major holds every used
+ * column, so the scan compares the query's ids on the exact columns with the row's.  exact_mask: bit f set = used column f (f <
+ * n_fields) is an exact-match column; at least one bit, none at or past n_fields, and at least one used column left to score, or the
+ * call fails.  A CANDIDATE of query q is a live row (below q's horizon) equal to q on every exact column.  All three take the pool in
+ * the three forms above (pool_form, header_dev, n_rows, capacity; n clamped to [0, capacity], head to [0, capacity)) and an optional
+ * before_dev [n_qry] int64 (device; NULL: no horizon), clamped to [0, n] as rat_bm25_topk_split_before clamps it.  They are chained
+ *     rat_bm25_exact_count -> rat_bm25_exact_plan -> rat_bm25_query_prepare_seg (first_row) -> rat_bm25_topk_split_exact
+ * on one stream with nothing read back, no allocation, no synchronisation and no floating-point atomics: capturable.  For one query
+ * batch the result equals rat_amd/retrieval.py's BM25_topk_retrieval_v4(live[:, used], ids[:, used], exact_match_col_indices, qry_batch_
+ * size = None) bit for bit, its two batch-wide rules included.
+ *
+ * rat_bm25_exact_count: out_counts[q] (int64 [n_qry]) = the number of candidates of query q.  ids [n_qry][row_stride] int32 are the
+ * request's encoded rows and cols [n_fields] int32 the used columns inside them, as rat_bm25_query_prepare takes them (a column is
+ * clamped to [0, row_stride)).  Work-group (tile of eight queries, range) counts range r = rows [r c, min((r + 1) c, n)), c = ceil(n /
+ * groups), into workspace[q][r]; a second launch sums a query's partials in range order — integer sums, one result whatever the grid.
+ * groups = 0: chosen from (n_qry, capacity) alone, at most RAT_BM25_EXACT_AUTO_GROUPS, so a captured launch never changes shape;
+ * 1 .. 4096 forces that many (a range past the end is empty).  workspace: 8 n_qry groups bytes, 8-byte aligned (groups = 0:
+ * 8 n_qry RAT_BM25_EXACT_AUTO_GROUPS always suffices).
+ *
+ * rat_bm25_exact_plan: one small launch over counts [n_qry].  first_row[q] (int64 [n_qry]) = the first query with a candidate, for
+ * every q, or 0 when no query has one — the shape rat_bm25_query_prepare_seg consumes, so the dtype rule of the IDF mapping looks at
+ * the first candidate-bearing query, as the offline path does after it has dropped the others.  listing_dev[0] (one int32) = 1 when
+ * no count exceeds topk (the LISTING rule holds for the call), else 0.  The counts are only compared: whatever they hold, first_row
+ * stays inside [0, n_qry) and the flag is 0 or 1.
+ *
+ * rat_bm25_topk_split_exact: rat_bm25_topk_split_before's two launches with the exact columns as a gate — in the field loop an exact
+ * column adds no weight, and after it a candidate scores (sum over the other columns, f ascending) + 1 and any other row 0, as
+ * rat_bm25_topk_grouped forms it; the horizon select, the lists, the merge and the total order (score descending, logical index
+ * ascending) are unchanged.  lens[q] = min(candidates, topk).  A third launch reads listing_dev[0] (int32, device): when it is not 0
+ * each query's entries are reordered by ascending logical index and their values set to 1.0 — every candidate is in the merged list
+ * then, nothing is rescanned; when it is 0 nothing changes.  qry_idf of an exact column is not read.  splits and workspace as
+ * rat_bm25_topk_split_before.  For ANY header, horizon, flag or weight content nothing outside the buffers is addressed. */
+#define RAT_BM25_EXACT_AUTO_GROUPS 256
+int rat_bm25_exact_count(const int32_t* db_ids_field_major, int pool_form, const int64_t* header_dev, int64_t n_rows, int64_t capacity,
+                         const int32_t* ids, const int32_t* cols, uint32_t exact_mask, const int64_t* before_dev, int64_t* out_counts,
+                         void* workspace, size_t workspace_bytes, int64_t n_qry, int row_stride, int n_fields, int groups, void* stream);
+int rat_bm25_exact_plan(const int64_t* counts, int64_t* first_row, int32_t* listing_dev, int64_t n_qry, int topk, void* stream);
+int rat_bm25_topk_split_exact(const int32_t* db_ids_field_major, int pool_form, const int64_t* header_dev, int64_t n_rows,
+                              int64_t capacity, const int32_t* qry_ids, const double* qry_idf, uint32_t exact_mask,
+                              const int64_t* before_dev, const int32_t* listing_dev, double* out_values, int64_t* out_indices,
+                              int64_t* out_lens, void* workspace, size_t workspace_bytes, int64_t n_qry, int n_fields, int topk,
+                              int splits, void* stream);
+
 /* ---- K3: prediction head -----------------------------------------------------------------------------
  * Plain fp32 GEMM on MFMA for MLP_Layer's nn.Linear (deep.py:126-141) forward / dgrad / wgrad:
  * C[M][N] = op(A) op(B) (+ bias[N]) (+ beta*C), row-major with leading dimensions, op = transpose flag. */

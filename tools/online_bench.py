@@ -40,6 +40,12 @@ query — the horizon excludes nothing, so the same rows are scored and the same
 pool form (immutable, capacity, window with the ring wrapped) at Q in {1, 16, 256}: what the compare and select per (row, query)
 cost; (ii) replayed score_rows(B indices) against replayed score(the same rows' ids) at B in {1, 16, 256}, host clock + synchronise,
 rounds of 200 alternating: what the gather and the horizon cost a request.
+--same — neighbours restricted to rows equal on given columns instead (profiles/online/same_bench.txt), same geometry, same = the user
+column: (i) device time per call of the chain rat_bm25_exact_count -> rat_bm25_exact_plan -> rat_bm25_topk_split_exact against the plain
+split scan of the same pool form (immutable, capacity, window with the ring wrapped) at Q in {1, 16, 256}, splits = 0 on both sides,
+measured as in --rows (i); the chain's result is compared bit for bit with the offline path (BM25_topk_retrieval_v4 with
+exact_match_col_indices) before anything is timed; (ii) replayed score(ids, same=) against replayed score(ids) at B in {1, 16, 256},
+host clock + synchronise, rounds of 200 alternating.
 There is no CPU fallback: without a GPU the tool exits with an error."""
 import argparse
 import os
@@ -713,6 +719,97 @@ def part_rows(emit, quick):
     emit("   (%d score_rows graphs, %d score() graphs)" % (len(scorer._rows_graphs), len(scorer._graphs)))
 
 
+def part_same(emit, quick):
+    from rat_amd import ops, retrieval
+    from rat_amd.online import OnlineScorer, RetrievalIndex
+    name, model, rows, vocab, cfg, n_pool, capacity = _movielens(quick)
+    dev, K, cols = torch.device("cuda:0"), cfg["topK"], cfg["used_col_indices"]
+    min_s = 0.05 if quick else MIN_TIMED_MS / 1e3
+    pool = rows(n_pool)
+    rs = np.random.RandomState(17)
+    same, mask = [cols[0]], 1
+    emit("== same (i): the chain alone [us per call, device time], %d-row pool (%d columns), K = %d, same = column %d (%d ids): "
+         "rat_bm25_exact_count -> rat_bm25_exact_plan -> rat_bm25_topk_split_exact against the plain split scan of the same pool form, "
+         "splits = 0 on both sides; hipGraphs of %d calls, device events, alternating" % (n_pool, len(cols), K, cols[0], vocab[0], REPS))
+    wrap = n_pool // 3
+    forms = (("immutable", {}, 0), ("capacity", dict(capacity=capacity), 0), ("window wrapped", dict(capacity=n_pool + wrap, window=True), 2 * wrap))
+    queries = {Q: np.stack([rs.randint(0, v, size=Q) for v in vocab], axis=1) for Q in (1, 16, 256)}
+
+    def offline_over(live):
+        return {Q: retrieval.BM25_topk_retrieval_v4(live[:, cols], q, exact_match_col_indices=[0], qry_batch_size=None, topK=K,
+                                                    device="cuda:0") for Q, q in queries.items()}
+    offline = offline_over(pool)
+    for label, kw, pushes in forms:
+        index = RetrievalIndex(pool, cols, K, dev, **kw)
+        live = pool
+        for _ in range(pushes // wrap):                                       # the window fills, then loses its oldest rows: the head moves
+            new = rows(wrap)
+            index.append(new)
+            live = np.concatenate([live, new])[-index.capacity:]
+        if pushes:
+            assert int(index.count[1]) + len(index) > index.capacity and len(live) == len(index), "the window does not wrap"
+            offline = offline_over(live)                                      # the offline path over the window's live rows, oldest first
+        form = index._pool_form()
+        for Q in (1, 16, 256):
+            ids = torch.from_numpy(queries[Q].astype(np.int32)).to(dev)
+            got = index.retrieve(ids, same=same)
+            for g, w in zip(got, offline[Q]):                                 # the offline path over the same live rows: the same bits
+                assert np.array_equal(g.cpu().numpy().view(np.int64), np.ascontiguousarray(w).view(np.int64)), (label, Q)
+            first_row, _flag = ops.bm25_exact_plan(ops.bm25_exact_count(index.db_t, ids, index.cols, mask, **form), K)
+            q_ids, q_idf = ops.bm25_query_prepare(ids, index.cols, index.table_ids, index.table_idf, index.table_offsets, first_row=first_row)
+            p_ids, p_idf = ops.bm25_query_prepare(ids, index.cols, index.table_ids, index.table_idf, index.table_offsets)
+            if index.window:
+                plain = lambda: ops.bm25_topk_split_ring(index.db_t, index.count, p_ids, p_idf, K)          # noqa: E731
+            elif index.capacity is not None:
+                plain = lambda: ops.bm25_topk_split_dev(index.db_t, index.count, p_ids, p_idf, K)           # noqa: E731
+            else:
+                plain = lambda: ops.bm25_topk_split(index.db_t, p_ids, p_idf, K)                            # noqa: E731
+
+            def chain():
+                counts = ops.bm25_exact_count(index.db_t, ids, index.cols, mask, **form)
+                _first, flag = ops.bm25_exact_plan(counts, K)
+                return ops.bm25_topk_split_exact(index.db_t, q_ids, q_idf, mask, flag, K, **form)
+
+            def count_only():
+                return ops.bm25_exact_count(index.db_t, ids, index.cols, mask, **form)
+            again = chain()
+            torch.cuda.synchronize()
+            for g, w in zip(again, got):
+                assert torch.equal(g.view(torch.int64), w.view(torch.int64)), (label, Q)
+            graphs = {"plain": _graph_of(plain, REPS)[0], "chain": _graph_of(chain, REPS)[0], "count": _graph_of(count_only, REPS)[0]}
+            ms = time_alternating(graphs, REPS, 50.0 if quick else MIN_TIMED_MS)
+            emit("%-14s Q %4d | plain %.1f | count + plan + exact scan %.1f (the count alone %.1f) | chain / plain = %.4f" %
+                 (label, Q, ms["plain"] * 1e3, ms["chain"] * 1e3, ms["count"] * 1e3, ms["chain"] / ms["plain"]))
+            del graphs
+        del index
+    emit("   (every form: retrieve(ids, same=) equals BM25_topk_retrieval_v4(live rows, ..., exact_match_col_indices=[0]) bit for bit at every Q)")
+
+    emit("== same (ii): replayed OnlineScorer.score(ids, same=) against replayed score(ids) [us per request], %s, immutable %d-row pool; "
+         "host clock + synchronise, rounds of 200 requests alternating" % (name, n_pool))
+    scorer = OnlineScorer(model, pool, cfg, graph=True)
+    for B in (1, 16, 256):
+        ids = torch.from_numpy(queries[B].astype(np.int32)).to(dev)
+        for _ in range(5):
+            y_same, y_plain = scorer.score(ids, same=same), scorer.score(ids)
+        torch.cuda.synchronize()
+        assert all(e[1] for e in scorer._same_graphs.values()) and all(e[1] for e in scorer._graphs.values()), "not captured"
+        per = {"same": [], "score": []}
+        while min(sum(v) for v in per.values()) * 200 / 1e6 < min_s or min(len(v) for v in per.values()) < 3:
+            per["same"].append(_replay_round(_SameSide(scorer, same), ids))
+            per["score"].append(_replay_round(scorer, ids))
+        a, b = (sum(per[k]) / len(per[k]) for k in ("same", "score"))
+        emit("B %4d | score(same=) %s | score %s | same / plain = %.4f | predictions differ: %s"
+             % (B, _stats(per["same"]), _stats(per["score"]), a / b, not torch.equal(y_same, y_plain)))
+    emit("   (%d score(same=) graphs, %d score() graphs)" % (len(scorer._same_graphs), len(scorer._graphs)))
+
+
+class _SameSide:
+    """score(ids, same=) behind the name _replay_round calls"""
+
+    def __init__(self, scorer, same):
+        self.score = lambda ids: scorer.score(ids, same=same)
+
+
 class _RowsSide:
     """score_rows behind the name _replay_round calls"""
 
@@ -730,6 +827,7 @@ def main():
     ap.add_argument("--find", action="store_true", help="measure the pool addressed by key (find against numpy; relabel; replay)")
     ap.add_argument("--requests", action="store_true", help="measure requests that share a launch (score_requests against R x score)")
     ap.add_argument("--rows", action="store_true", help="measure the pool that looks at itself (horizon scan against the plain scan; score_rows)")
+    ap.add_argument("--same", action="store_true", help="measure neighbours restricted to equal columns (the chain against the plain scan; score(same=))")
     ap.add_argument("--trace", action="store_true", help="with --delete: only a few deletions per point, for a kernel trace")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -761,6 +859,9 @@ def main():
         return
     if args.rows:
         part_rows(emit, args.quick)
+        return
+    if args.same:
+        part_same(emit, args.quick)
         return
     part1(emit, args.quick)
     part2(emit, args.quick)

@@ -106,6 +106,8 @@ struct SplitArgs {
                              // POOL_RING: that header is two words, {row count, physical slot of the oldest live row}
     int64_t stride;          // POOL_DEV / POOL_RING: column stride of db_t (the capacity); otherwise the stride is N
     const int64_t* before;   // [Q], HORIZON only: query q sees the logical rows i < before[q]
+    uint32_t exact_mask;     // EXACT only: bit f set = used column f is an exact-match column (it gates a row, it adds no weight)
+    const int32_t* listing;  // EXACT only: one word, != 0 = the listing rule holds for this call (bm25_exact_list_kernel)
 };
 
 // Where the scan takes the pool's extent from.
@@ -123,8 +125,15 @@ enum { POOL_HOST = 0, POOL_DEV = 1, POOL_RING = 2 };
 // the sums, their order and the total order are those of the plain scan over the rows [0, before[q]).  Ranges are still cut over
 // [0, N), and a work-group whose range lies past every horizon of its tile scans it all the same (nothing here is tuned).
 // POOL_HOST with HORIZON takes the column stride from a.stride (the pool's capacity), the row count from a.N.
-template <int KMAX, int QT, int RU, int POOL, bool HORIZON>
+//
+// EXACT (rat_bm25_topk_split_exact; always with HORIZON, whose list may be null here: no horizon, every query sees [0, N)): the
+// used columns in a.exact_mask are exact-match columns.  In the field loop such a column adds no weight; it ANDs "row equals query
+// here" into a gate, one bit per (row, query) of the trip.  After the loop a row inside the gate scores (sum + 1) — the sum over the
+// remaining columns, f ascending, as rat_bm25_topk_grouped forms it — and any other row 0, before the horizon select.  A candidate
+// scores at least 1, so it is positive; insertion, wave merge, ranking and bm25_merge_kernel are the same code.
+template <int KMAX, int QT, int RU, int POOL, bool HORIZON, bool EXACT = false>
 __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a) {
+    static_assert(!EXACT || (HORIZON && RU * QT <= 32), "the exact-match scan has the horizon select and one gate word per trip");
     __shared__ WaveTile<QT> tile_s[ON_WAVES];
     __shared__ double wl_v[ON_WAVES][QT][KMAX];          // the K best of every wave, ranked against each other after the barrier
     __shared__ int64_t wl_i[ON_WAVES][QT][KMAX];
@@ -157,7 +166,11 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
 #pragma unroll
             for (int t = 0; t < QT; ++t) {
                 const int64_t q = q0 + t < a.Q ? q0 + t : a.Q - 1;            // wave-uniform: scalar loads
-                const int64_t b = a.before[q];
+                int64_t b = N;
+                if constexpr (!EXACT)
+                    b = a.before[q];
+                else if (a.before != nullptr)
+                    b = a.before[q];
                 bef[t] = b < 0 ? 0 : (b > N ? N : b);
             }
         }
@@ -180,6 +193,7 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
             for (int u = 0; u < RU; ++u)
 #pragma unroll
                 for (int t = 0; t < QT; ++t) s[u][t] = 0.0;
+            [[maybe_unused]] uint32_t gate = ~0u;          // EXACT: bit u * QT + t = row u equals query t on every exact column so far
             for (int f = 0; f < a.F; ++f) {
                 int32_t id[RU];
 #pragma unroll
@@ -196,10 +210,24 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
                 for (int t = 0; t < QT; ++t) {
                     const int64_t q = q0 + t < a.Q ? q0 + t : a.Q - 1;                    // wave-uniform: scalar loads
                     const int32_t qid = a.qry[q * a.F + f];
+                    if constexpr (EXACT) {
+                        if ((a.exact_mask >> f) & 1u) {                                   // wave-uniform: the column gates, it adds nothing
+#pragma unroll
+                            for (int u = 0; u < RU; ++u) gate &= ~((uint32_t)(qid != id[u]) << (u * QT + t));
+                            continue;
+                        }
+                    }
                     const double w = a.idf[q * a.F + f];
 #pragma unroll
                     for (int u = 0; u < RU; ++u) s[u][t] += (qid == id[u] && n0 + (int64_t)u * ON_THREADS < hi) ? w : 0.0;
                 }
+            }
+            if constexpr (EXACT) {                         // (sum + 1) inside the gate, 0 outside; a row past the range is outside
+#pragma unroll
+                for (int u = 0; u < RU; ++u)
+#pragma unroll
+                    for (int t = 0; t < QT; ++t)
+                        s[u][t] = (((gate >> (u * QT + t)) & 1u) != 0 && n0 + (int64_t)u * ON_THREADS < hi) ? s[u][t] + 1.0 : 0.0;
             }
             if constexpr (HORIZON) {
 #pragma unroll
@@ -345,6 +373,31 @@ __global__ void __launch_bounds__(64) bm25_merge_kernel(SplitArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------ pass 3 (EXACT): listing
+// The listing rule of the exact-match retrieval (rat_amd/retrieval.py: no group of the call is larger than K): a query's entries are
+// its candidates in ascending logical index, each with value 1.0.  Every candidate scored >= 1 and there are at most K of them, so the
+// merged list already holds them all, in score order: one wave per query gives entry k the slot (number of valid entries with a lower
+// index) — the indices are distinct, the valid entries stand in front — and nothing is rescanned.  *listing == 0: nothing to do.
+__global__ void __launch_bounds__(64) bm25_exact_list_kernel(SplitArgs a) {
+    if (a.listing[0] == 0) return;                     // the same in every thread of the grid
+    const int lane = rat_lane();
+    for (int64_t q = blockIdx.x; q < a.Q; q += gridDim.x) {
+        int64_t* idx = a.out_idx + q * a.K;
+        const int64_t mine = lane < a.K ? idx[lane] : -1;
+        int rank = 0;
+        for (int j = 0; j < a.K; ++j) {
+            const int64_t other = idx[j];
+            rank += (other >= 0 && mine >= 0 && other < mine) ? 1 : 0;         // rank < K: at most K - 1 others
+        }
+        __syncthreads();                               // every entry is read before one is overwritten
+        if (mine >= 0) {
+            idx[rank] = mine;
+            a.out_val[q * a.K + rank] = 1.0;
+        }
+        __syncthreads();
+    }
+}
+
 int64_t auto_splits(int64_t n_qry, int64_t n_db, int topk) {
     const int64_t tiles = topk <= 8 ? (n_qry + 3) / 4 : n_qry;
     if (tiles >= ON_SINGLE_TILES) return 1;
@@ -357,10 +410,12 @@ int64_t auto_splits(int64_t n_qry, int64_t n_db, int topk) {
 
 // the three entry points of the split scan: the same two launches, the scan instantiated with the row count by value, from the device,
 // or with the ring's header from the device
-template <int POOL, bool HORIZON = false>
+// EXACT: the scan with the exact-match gate, the same merge, then the listing pass
+template <int POOL, bool HORIZON = false, bool EXACT = false>
 int launch_split(const char* who, const int32_t* db_t, const int32_t* qry_ids, const double* qry_idf, double* out_values,
                  int64_t* out_indices, int64_t* out_lens, void* workspace, size_t workspace_bytes, int64_t n_db, const int64_t* n_dev,
-                 int64_t stride, int64_t n_qry, int n_fields, int topk, int splits, void* stream, const int64_t* before = nullptr) {
+                 int64_t stride, int64_t n_qry, int n_fields, int topk, int splits, void* stream, const int64_t* before = nullptr,
+                 uint32_t exact_mask = 0, const int32_t* listing = nullptr) {
     const size_t need = (size_t)n_qry * (size_t)splits * (size_t)topk * (sizeof(double) + sizeof(int64_t));
     if (workspace == nullptr || workspace_bytes < need)
         return rat_fail(std::string(who) + ": workspace smaller than rat_bm25_topk_split_workspace()");
@@ -382,15 +437,21 @@ int launch_split(const char* who, const int32_t* db_t, const int32_t* qry_ids, c
     a.n_dev = n_dev;
     a.stride = stride;
     a.before = before;
+    a.exact_mask = exact_mask;
+    a.listing = listing;
     if (topk <= 8) {
         const int64_t items = (n_qry + 3) / 4 * splits;
-        RAT_LAUNCH((bm25_scan_split_kernel<8, 4, 4, POOL, HORIZON>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
+        RAT_LAUNCH((bm25_scan_split_kernel<8, 4, 4, POOL, HORIZON, EXACT>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
     } else {
         const int64_t items = n_qry * splits;
-        RAT_LAUNCH((bm25_scan_split_kernel<32, 1, 4, POOL, HORIZON>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
+        RAT_LAUNCH((bm25_scan_split_kernel<32, 1, 4, POOL, HORIZON, EXACT>), (unsigned)(items < 65536 ? items : 65536), ON_THREADS, 0, stream, a);
     }
     if (rat_check_launch(who) != 0) return -1;
     RAT_LAUNCH(bm25_merge_kernel, (unsigned)(n_qry < 65536 ? n_qry : 65536), 64, 0, stream, a);
+    if constexpr (EXACT) {
+        if (rat_check_launch(who) != 0) return -1;
+        RAT_LAUNCH(bm25_exact_list_kernel, (unsigned)(n_qry < 65536 ? n_qry : 65536), 64, 0, stream, a);
+    }
     return rat_check_launch(who);
 }
 
@@ -1133,4 +1194,229 @@ extern "C" int rat_bm25_topk_split_before(const int32_t* db_ids_field_major, int
                                             workspace_bytes, 0, header_dev, capacity, n_qry, n_fields, topk, splits, stream, before_dev);
     return launch_split<POOL_RING, true>(who, db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
                                          workspace_bytes, 0, header_dev, capacity, n_qry, n_fields, topk, splits, stream, before_dev);
+}
+
+// ------------------------------------------------------------------------------------------------------------ neighbours equal on given columns
+// Exact-match retrieval on the request path (rat_amd/retrieval.py: exact_match_col_indices; the offline job numbers the groups on the
+// host and hands them to rat_bm25_topk_grouped).  Here nobody numbers anything: the scan compares the query's ids on the exact columns
+// with the row's ids — db_t holds every used column — and the two batch-wide rules of the offline path are decided on the device from
+// the candidate counts, with nothing read back:
+//   rat_bm25_exact_count   c[q] = live rows (below q's horizon) equal to query q on every exact column: work-group (query tile, range)
+//                          counts its range into ws[q][range], a second launch sums a query's partials in range order — integers,
+//                          one result whatever the grid
+//   rat_bm25_exact_plan    first_row[q] = the first query with a candidate (what rat_bm25_query_prepare_seg takes its dtype rule
+//                          from: the offline path drops candidate-less queries before it maps the weights), and the listing flag
+//   rat_bm25_topk_split_exact   the gated scan, the merge and the listing pass (launch_split<POOL, true, true>)
+namespace {
+
+constexpr int EC_THREADS = 256;
+constexpr int EC_WAVES = EC_THREADS / 64;
+constexpr int EC_QT = 8;                               // queries per work-group: their ids on the exact columns are staged in LDS
+static_assert(ON_FMAX * EC_QT <= EC_THREADS, "one thread stages one (exact column, query) id");
+constexpr int EC_MAX_GROUPS = 4096;
+// groups = 0: from the capacity and the number of queries only — enough ranges for EC_TARGET_GROUPS work-groups (the kernel is small:
+// a CU holds many), every range at least one full trip of four waves over four rows each, at most RAT_BM25_EXACT_AUTO_GROUPS
+constexpr int64_t EC_TARGET_GROUPS = 1024;
+constexpr int64_t EC_MIN_RANGE_ROWS = 1024;
+
+struct ExactCountArgs {
+    const int32_t* db_t;     // [F][capacity]
+    const int32_t* ids;      // [Q][row_stride] the request's encoded rows
+    const int32_t* cols;     // [F] used column f -> its column of `ids`, clamped to [0, row_stride)
+    const int64_t* header;
+    const int64_t* before;   // [Q] or null
+    int64_t* ws;             // [Q][groups]
+    int64_t* counts;         // [Q]
+    int64_t N, capacity, Q;
+    int row_stride, F, groups;
+    uint32_t mask;
+};
+
+template <int POOL>
+__global__ void __launch_bounds__(EC_THREADS) bm25_exact_count_kernel(ExactCountArgs a) {
+    __shared__ int wave_sum[EC_WAVES][EC_QT];
+    __shared__ int32_t qid_s[ON_FMAX][EC_QT];          // the tile's ids on the exact columns, exact column e = 0 .. n_exact - 1
+    __shared__ int field_s[ON_FMAX];                   // exact column e -> its used column f
+    const int tid = threadIdx.x, lane = rat_lane(), wave = rat_wave();
+    const PoolView v = pool_view<POOL>(a.header, a.N, a.capacity);
+    int n_exact = 0;                                   // the same in every thread: the mask is a kernel argument
+    for (int f = 0; f < a.F; ++f) {
+        if (((a.mask >> f) & 1u) == 0) continue;
+        if (tid == 0) field_s[n_exact] = f;
+        ++n_exact;
+    }
+    const int64_t R = (v.n + a.groups - 1) / a.groups;
+    const int64_t ntiles = (a.Q + EC_QT - 1) / EC_QT;
+    for (int64_t item = blockIdx.x; item < ntiles * a.groups; item += gridDim.x) {
+        const int64_t q0 = (item / a.groups) * EC_QT;
+        const int64_t g = item % a.groups;
+        const int64_t lo = g * R < v.n ? g * R : v.n;                          // ranges past the end of the pool are empty
+        const int64_t hi = lo + R < v.n ? lo + R : v.n;
+        int64_t bef[EC_QT];
+#pragma unroll
+        for (int t = 0; t < EC_QT; ++t) {
+            const int64_t q = q0 + t < a.Q ? q0 + t : a.Q - 1;                 // wave-uniform: scalar loads
+            const int64_t b = a.before != nullptr ? a.before[q] : v.n;
+            bef[t] = b < 0 ? 0 : (b > v.n ? v.n : b);
+        }
+        // the tile's query ids are staged once per item: the row loop reads them from LDS (one address per wave: a broadcast)
+        __syncthreads();                               // field_s is written; the previous item has read qid_s
+        if (tid < n_exact * EC_QT) {
+            const int e = tid / EC_QT, t = tid % EC_QT;
+            const int64_t q = q0 + t < a.Q ? q0 + t : a.Q - 1;
+            int col = a.cols[field_s[e]];
+            col = col < 0 ? 0 : (col >= a.row_stride ? a.row_stride - 1 : col);
+            qid_s[e][t] = a.ids[q * a.row_stride + col];
+        }
+        __syncthreads();
+        int count[EC_QT];
+#pragma unroll
+        for (int t = 0; t < EC_QT; ++t) count[t] = 0;
+        for (int64_t i = lo + tid; i < hi; i += EC_THREADS) {
+            const int64_t slot = ring_wrap(v.head + i, a.capacity);
+            uint32_t equal = (1u << EC_QT) - 1u;
+            for (int e = 0; e < n_exact; ++e) {
+                const int32_t id = a.db_t[(int64_t)field_s[e] * a.capacity + slot];
+#pragma unroll
+                for (int t = 0; t < EC_QT; ++t) equal &= ~((uint32_t)(qid_s[e][t] != id) << t);
+            }
+#pragma unroll
+            for (int t = 0; t < EC_QT; ++t) count[t] += (((equal >> t) & 1u) != 0 && i < bef[t]) ? 1 : 0;
+        }
+#pragma unroll
+        for (int t = 0; t < EC_QT; ++t) {
+            int c = count[t];
+            for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
+            if (lane == 0) wave_sum[wave][t] = c;
+        }
+        __syncthreads();
+        if (tid < EC_QT && q0 + tid < a.Q) {
+            int64_t sum = 0;
+            for (int w = 0; w < EC_WAVES; ++w) sum += wave_sum[w][tid];
+            a.ws[(q0 + tid) * a.groups + g] = sum;
+        }
+        __syncthreads();                               // the next item reuses wave_sum
+    }
+}
+
+__global__ void __launch_bounds__(256) bm25_exact_sum_kernel(const int64_t* ws, int64_t* counts, int64_t Q, int groups) {
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < Q; q += (int64_t)gridDim.x * 256) {
+        int64_t sum = 0;
+        for (int g = 0; g < groups; ++g) sum += ws[q * groups + g];
+        counts[q] = sum;
+    }
+}
+
+// one work-group: the first query with a candidate (Q when there is none) and the largest count, a minimum and a maximum through LDS.
+// The counts are only compared — whatever they hold, first_row stays inside [0, Q) and the flag is 0 or 1.
+__global__ void __launch_bounds__(256) bm25_exact_plan_kernel(const int64_t* counts, int64_t* first_row, int32_t* listing, int64_t Q,
+                                                              int K) {
+    __shared__ int64_t first_s[256];
+    __shared__ int64_t most_s[256];
+    const int tid = threadIdx.x;
+    int64_t first = Q, most = 0;
+    for (int64_t q = tid; q < Q; q += 256) {
+        const int64_t c = counts[q];
+        if (c > 0 && q < first) first = q;
+        most = c > most ? c : most;
+    }
+    first_s[tid] = first;
+    most_s[tid] = most;
+    __syncthreads();
+    for (int step = 128; step > 0; step >>= 1) {
+        if (tid < step) {
+            first_s[tid] = first_s[tid + step] < first_s[tid] ? first_s[tid + step] : first_s[tid];
+            most_s[tid] = most_s[tid + step] > most_s[tid] ? most_s[tid + step] : most_s[tid];
+        }
+        __syncthreads();
+    }
+    first = first_s[0] < Q ? first_s[0] : 0;
+    for (int64_t q = tid; q < Q; q += 256) first_row[q] = first;
+    if (tid == 0) listing[0] = most_s[0] <= K ? 1 : 0;
+}
+
+int64_t auto_count_groups(int64_t n_qry, int64_t capacity) {
+    const int64_t tiles = (n_qry + EC_QT - 1) / EC_QT;
+    int64_t g = (EC_TARGET_GROUPS + tiles - 1) / tiles;
+    const int64_t by_rows = capacity / EC_MIN_RANGE_ROWS;
+    if (g > by_rows) g = by_rows;
+    if (g > RAT_BM25_EXACT_AUTO_GROUPS) g = RAT_BM25_EXACT_AUTO_GROUPS;
+    return g < 1 ? 1 : g;
+}
+
+// the exact columns as one bit per used column: at least one, none past the used columns, and a column left to score
+bool exact_mask_ok(uint32_t mask, int n_fields) {
+    const uint32_t all = n_fields >= 32 ? ~0u : ((1u << n_fields) - 1u);
+    return mask != 0 && (mask & ~all) == 0 && mask != all;
+}
+
+}  // namespace
+
+extern "C" int rat_bm25_exact_count(const int32_t* db_ids_field_major, int pool_form, const int64_t* header_dev, int64_t n_rows,
+                                    int64_t capacity, const int32_t* ids, const int32_t* cols, uint32_t exact_mask,
+                                    const int64_t* before_dev, int64_t* out_counts, void* workspace, size_t workspace_bytes,
+                                    int64_t n_qry, int row_stride, int n_fields, int groups, void* stream) {
+    RAT_REQUIRE(db_ids_field_major && ids && cols && out_counts && workspace, "null pointer");
+    RAT_REQUIRE(pool_form == POOL_HOST || pool_form == POOL_DEV || pool_form == POOL_RING, "pool_form must be 0, 1 or 2");
+    RAT_REQUIRE(pool_form == POOL_HOST || header_dev, "null header");
+    RAT_REQUIRE(capacity > 0 && n_qry > 0 && n_fields > 0 && row_stride > 0, "bad dims");
+    RAT_REQUIRE(pool_form != POOL_HOST || (n_rows >= 0 && n_rows <= capacity), "n_rows outside [0, capacity]");
+    RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
+    RAT_REQUIRE(exact_mask_ok(exact_mask, n_fields), "exact_mask must name at least one used column and leave at least one to score");
+    RAT_REQUIRE(groups >= 0 && groups <= EC_MAX_GROUPS, "groups must be 0 (library's choice) or 1..4096");
+    if (groups == 0) groups = (int)auto_count_groups(n_qry, capacity);         // from the capacity: a captured launch keeps its shape
+    RAT_REQUIRE((capacity + groups - 1) / groups <= INT32_MAX, "more than 2^31 - 1 rows per range: pass more groups");
+    RAT_REQUIRE(workspace_bytes / sizeof(int64_t) / (size_t)n_qry >= (size_t)groups, "workspace smaller than 8 n_qry groups bytes");
+    RAT_REQUIRE(((uintptr_t)workspace & 7) == 0, "workspace must be 8-byte aligned");
+    ExactCountArgs a{db_ids_field_major, ids, cols, header_dev, before_dev, static_cast<int64_t*>(workspace), out_counts, n_rows,
+                     capacity, n_qry, row_stride, n_fields, groups, exact_mask};
+    const int64_t items = (n_qry + EC_QT - 1) / EC_QT * groups;
+    const unsigned grid = (unsigned)(items < 65536 ? items : 65536);
+    if (pool_form == POOL_HOST)
+        RAT_LAUNCH(bm25_exact_count_kernel<POOL_HOST>, grid, EC_THREADS, 0, stream, a);
+    else if (pool_form == POOL_DEV)
+        RAT_LAUNCH(bm25_exact_count_kernel<POOL_DEV>, grid, EC_THREADS, 0, stream, a);
+    else
+        RAT_LAUNCH(bm25_exact_count_kernel<POOL_RING>, grid, EC_THREADS, 0, stream, a);
+    if (rat_check_launch("rat_bm25_exact_count") != 0) return -1;
+    const int64_t blocks = (n_qry + 255) / 256;
+    RAT_LAUNCH(bm25_exact_sum_kernel, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a.ws, out_counts, n_qry, groups);
+    return rat_check_launch("rat_bm25_exact_count");
+}
+
+extern "C" int rat_bm25_exact_plan(const int64_t* counts, int64_t* first_row, int32_t* listing_dev, int64_t n_qry, int topk,
+                                   void* stream) {
+    RAT_REQUIRE(counts && first_row && listing_dev, "null pointer");
+    RAT_REQUIRE(n_qry > 0 && topk > 0, "bad dims");
+    RAT_LAUNCH(bm25_exact_plan_kernel, 1u, 256, 0, stream, counts, first_row, listing_dev, n_qry, topk);
+    return rat_check_launch("rat_bm25_exact_plan");
+}
+
+extern "C" int rat_bm25_topk_split_exact(const int32_t* db_ids_field_major, int pool_form, const int64_t* header_dev, int64_t n_rows,
+                                         int64_t capacity, const int32_t* qry_ids, const double* qry_idf, uint32_t exact_mask,
+                                         const int64_t* before_dev, const int32_t* listing_dev, double* out_values,
+                                         int64_t* out_indices, int64_t* out_lens, void* workspace, size_t workspace_bytes,
+                                         int64_t n_qry, int n_fields, int topk, int splits, void* stream) {
+    RAT_REQUIRE(db_ids_field_major && qry_ids && qry_idf && listing_dev && out_values && out_indices && out_lens, "null pointer");
+    RAT_REQUIRE(pool_form == POOL_HOST || pool_form == POOL_DEV || pool_form == POOL_RING, "pool_form must be 0, 1 or 2");
+    RAT_REQUIRE(pool_form == POOL_HOST || header_dev, "null header");
+    RAT_REQUIRE(capacity > 0 && n_qry > 0 && n_fields > 0 && topk > 0, "bad dims");
+    RAT_REQUIRE(pool_form != POOL_HOST || (n_rows >= 0 && n_rows <= capacity), "n_rows outside [0, capacity]");
+    RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
+    RAT_REQUIRE(topk <= ON_KMAX, "topK > 32 is not supported");
+    RAT_REQUIRE(exact_mask_ok(exact_mask, n_fields), "exact_mask must name at least one used column and leave at least one to score");
+    RAT_REQUIRE(splits >= 0 && splits <= ON_MAX_SPLITS, "splits must be 0 (library's choice) or 1..4096");
+    if (splits == 0) splits = (int)auto_splits(n_qry, capacity, topk);        // from the capacity, as rat_bm25_topk_split_before
+    const char* who = "rat_bm25_topk_split_exact";
+    if (pool_form == POOL_HOST)
+        return launch_split<POOL_HOST, true, true>(who, db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
+                                                   workspace_bytes, n_rows, nullptr, capacity, n_qry, n_fields, topk, splits, stream,
+                                                   before_dev, exact_mask, listing_dev);
+    if (pool_form == POOL_DEV)
+        return launch_split<POOL_DEV, true, true>(who, db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
+                                                  workspace_bytes, 0, header_dev, capacity, n_qry, n_fields, topk, splits, stream,
+                                                  before_dev, exact_mask, listing_dev);
+    return launch_split<POOL_RING, true, true>(who, db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
+                                               workspace_bytes, 0, header_dev, capacity, n_qry, n_fields, topk, splits, stream,
+                                               before_dev, exact_mask, listing_dev);
 }

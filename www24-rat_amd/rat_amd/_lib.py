@@ -175,6 +175,12 @@ _SIGNATURES = {
     "rat_pool_gather_rows": (c_int, [_P, _P, c_int, _P, c_int64, c_int64, _P, _P, _P, _P, c_int64, c_int, _P]),
     "rat_bm25_topk_split_before": (c_int, [_P, c_int, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t, c_int64, c_int, c_int,
                                            c_int, _P]),
+    # neighbours restricted to rows equal on given columns: candidate counts, the batch-wide plan, and the gated scan
+    "rat_bm25_exact_count": (c_int, [_P, c_int, _P, c_int64, c_int64, _P, _P, ctypes.c_uint32, _P, _P, _P, c_size_t, c_int64, c_int, c_int,
+                                     c_int, _P]),
+    "rat_bm25_exact_plan": (c_int, [_P, _P, _P, c_int64, c_int, _P]),
+    "rat_bm25_topk_split_exact": (c_int, [_P, c_int, _P, c_int64, c_int64, _P, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, c_size_t,
+                                          c_int64, c_int, c_int, c_int, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -65,8 +65,22 @@ labels as ``y_true``, so it feeds ``model.train_step`` as well as the eval forwa
 ``graph=True`` the chain gather -> prepare -> scan -> assemble -> forward of a size is captured like a request's, in a dictionary of
 its own.
 
-Not served online (refused at construction): exact-match columns (numbering the groups needs a host ``np.unique`` over pool and
-queries), label-wise retrieval, topK > 32, more than 32 retrieval columns, data-parallel models.  Rows are deleted from a
+Neighbours can be restricted to rows equal on given columns.  ``retrieve(ids, same=cols)``, ``batch / score(ids, same=cols)`` and
+``batch_rows / score_rows / evaluate_rows(indices, same=cols)`` take a row's candidates only from the live rows that EQUAL it on the
+columns ``cols`` (used columns of the index; at least one used column must remain to score) — the reference's
+``exact_match_col_indices``, "this user's history", offered per call so that one resident pool serves both kinds of request.  No group
+is numbered: ``db_t`` holds every used column, and the scan compares ids.  The chain is ``rat_bm25_exact_count`` (candidates per
+query, through the pool form and below the horizon) -> ``rat_bm25_exact_plan`` (the first query with a candidate, whose row decides the
+mapping's dtype rule, and whether the call LISTS: no query has more than K candidates) -> ``rat_bm25_query_prepare_seg`` ->
+``rat_bm25_topk_split_exact`` (an exact column gates a row instead of adding a weight, a candidate scores BM25 + 1; a listing call
+returns the candidates in ascending index with value 1.0), nothing read back in between, and the result equals
+``retrieval.BM25_topk_retrieval_v4(live[:, U], ids[:, U], exact_match_col_indices=E, qry_batch_size=None)`` bit for bit.  With
+``graph=True`` the chains of ``score(ids, same=)`` and ``score_rows(indices, same=)`` are captured in dictionaries of their own, keyed
+by the columns as well; the ``same=None`` paths and their graphs are untouched.
+
+Not served online (refused at construction): the config keys ``exact_match_cols`` / ``exact_match_col_indices`` (the restriction is
+per call, ``same=``; not built: ``same`` with ``request_offsets``, and all used columns exact), label-wise retrieval, topK > 32, more
+than 32 retrieval columns, data-parallel models.  Rows are deleted from a
 ``window=True`` pool only: the append-only form reserves its IDF tables for the rows that can still come, which deletions would undo.
 """
 import numpy as np
@@ -221,6 +235,31 @@ def _before_list(before, B, device):
     return torch.from_numpy(np.ascontiguousarray(b.astype(np.int64))).to(device, non_blocking=True)
 
 
+def _same_positions(same, col_list):
+    """what ``retrieve(ids, same=...)`` takes -> the positions of those columns inside the index's used columns (a tuple, ascending:
+    the order in which the caller names the columns means nothing), or ValueError: a non-empty 1-D list of distinct integer column numbers of the encoded row, each a used column,
+    and at least one used column left to score"""
+    if torch.is_tensor(same):
+        same = same.detach().cpu().numpy()
+    c = np.asarray(same)
+    if c.ndim != 1 or c.size == 0:
+        raise ValueError("same takes a non-empty 1-D list of column numbers, got shape %s" % (tuple(c.shape),))
+    if not np.issubdtype(c.dtype, np.integer):
+        raise ValueError("same takes integer column numbers, got dtype %s" % c.dtype)
+    c = [int(x) for x in c]
+    if len(set(c)) != len(c):
+        raise ValueError("same: repeated column in %s" % (c,))
+    if any(x not in col_list for x in c):
+        raise ValueError("same: column %s is not a used column of this index (%s)" % ([x for x in c if x not in col_list], col_list))
+    if len(c) >= len(col_list):
+        raise ValueError("same covers all %d used columns: at least one used column must remain to score" % len(col_list))
+    return tuple(sorted(col_list.index(x) for x in c))
+
+
+class _Exact(tuple):
+    """positions of the ``same`` columns inside the used columns, ascending, validated: what the scorer hands on internally"""
+
+
 class RetrievalIndex:
     """A retrieval pool resident in HBM: its id columns field-major (what the top-K scan streams) and its per-column IDF tables
     (built once, on the host, by ``retrieval.idf_tables`` — numpy's float64 ``log``, so the weights are bit-identical to the offline
@@ -276,7 +315,7 @@ class RetrievalIndex:
         self.table_idf = up(np.concatenate([w for _, w in tables]).astype(np.float64))
         self.table_offsets = up(np.concatenate([[0], np.cumsum([len(v) for v, _ in tables])]).astype(np.int64))
 
-    def retrieve(self, ids, request_offsets=None, _first_row=None, before=None):
+    def retrieve(self, ids, request_offsets=None, _first_row=None, before=None, same=None, _exact=None):
         """ids [B, L] (full encoded rows) -> (values fp64 [B, K], indices int64 [B, K] with -1 padding, lens int64 [B]), on the device.
         With ``window=True`` the indices are LOGICAL positions (0 = the oldest live row, len(index) - 1 = the newest): they hold until
         the next eviction (an ``evict``, or an ``append`` into a full window) or ``delete``, which renumber the rows.
@@ -289,7 +328,21 @@ class RetrievalIndex:
         the result equals, bit for bit, a retrieval of the same weights over a copy of the rows [0, before[q])
         (``rat_bm25_topk_split_before``).  The weights are those of the WHOLE live pool.  A host array is validated (ValueError,
         nothing launched: not 1-D, not integer, not B entries); a device tensor is used unread.  Not combined with
-        ``request_offsets`` (ValueError)."""
+        ``request_offsets`` (ValueError).
+        ``same`` (a non-empty 1-D list of distinct column numbers of the encoded row, as ``find`` takes them; each a used column, and
+        at least one used column left over): row q's candidates are only the live rows (below ``before[q]``, when given) that EQUAL
+        it on those columns, scored over the remaining used columns — the reference's ``exact_match_col_indices``.  The result equals,
+        bit for bit, ``retrieval.BM25_topk_retrieval_v4(live[:, U], ids[:, U], exact_match_col_indices=E, qry_batch_size=None,
+        topK=K)`` (U the used columns, E the positions of ``same`` in U), the offline path's batch-wide rules included: with no more
+        than K candidates for any row of the call every list is the candidates in ascending index with value 1.0; otherwise a
+        candidate scores BM25 + 1 and the dtype rule of the weights looks at the first row that has a candidate.  Nothing is read
+        back (``rat_bm25_exact_count`` -> ``rat_bm25_exact_plan`` -> ``rat_bm25_query_prepare_seg`` -> ``rat_bm25_topk_split_exact``).
+        A bad ``same`` is a ValueError with nothing launched; so is ``same`` with ``request_offsets``."""
+        exact = _exact                                 # (an OnlineScorer passes the positions it has validated already)
+        if same is not None:
+            if request_offsets is not None or _first_row is not None:
+                raise ValueError("same cannot be combined with request_offsets: groups inside request segments are not supported")
+            exact = _same_positions(same, self._col_list)
         if before is not None and (request_offsets is not None or _first_row is not None):
             raise ValueError("before cannot be combined with request_offsets: horizons inside request segments are not supported")
         ids = _as_device_ids(ids, self.device)
@@ -301,6 +354,8 @@ class RetrievalIndex:
             _first_row = _first_rows(*_request_offsets(request_offsets, ids.shape[0]), ids.shape[0], self.device)
         if before is not None:
             before = _before_list(before, ids.shape[0], self.device)
+        if exact is not None:
+            return self._retrieve_same(ids, before, sum(1 << f for f in exact))
         qry_ids, qry_idf = ops.bm25_query_prepare(ids, self.cols, self.table_ids, self.table_idf, self.table_offsets,
                                                   first_row=_first_row, lib=self._lib)
         if before is not None:
@@ -311,6 +366,17 @@ class RetrievalIndex:
         if self.capacity is not None:
             return ops.bm25_topk_split_dev(self.db_t, self.count, qry_ids, qry_idf, self.topK, splits=self.splits, lib=self._lib)
         return ops.bm25_topk_split(self.db_t, qry_ids, qry_idf, self.topK, splits=self.splits, lib=self._lib)
+
+    def _retrieve_same(self, ids, before, mask):
+        """count -> plan -> prepare -> gated scan, chained on the stream: the counts, the first candidate-bearing row and the listing
+        flag stay on the device"""
+        form = self._pool_form()
+        counts = ops.bm25_exact_count(self.db_t, ids, self.cols, mask, before=before, groups=self.splits, lib=self._lib, **form)
+        first_row, listing = ops.bm25_exact_plan(counts, self.topK, lib=self._lib)
+        qry_ids, qry_idf = ops.bm25_query_prepare(ids, self.cols, self.table_ids, self.table_idf, self.table_offsets,
+                                                  first_row=first_row, lib=self._lib)
+        return ops.bm25_topk_split_exact(self.db_t, qry_ids, qry_idf, mask, listing, self.topK, before=before, splits=self.splits,
+                                         lib=self._lib, **form)
 
     def __len__(self):
         return self.n_db
@@ -525,13 +591,13 @@ class RetrievalIndex:
 class _RequestGraph:
     """retrieve -> assemble -> eval forward of one request size as one linear hipGraph (one stream, no parallel branches)"""
 
-    def __init__(self, scorer, ids):
+    def __init__(self, scorer, ids, same=None):
         self.static_ids = ids.clone()
         self._stream = torch.cuda.Stream(device=ids.device)
         self.graph = torch.cuda.CUDAGraph()
         torch.cuda.synchronize()
         with torch.no_grad(), torch.cuda.graph(self.graph, stream=self._stream, capture_error_mode="thread_local"):
-            self.y_pred = scorer._score_eager(self.static_ids)
+            self.y_pred = scorer._score_eager(self.static_ids, same=same)
 
     def run(self, ids):
         if ids.data_ptr() != self.static_ids.data_ptr():
@@ -544,13 +610,13 @@ class _RowsGraph:
     """gather -> prepare -> horizon scan -> assemble -> eval forward of one number of pool rows as one linear hipGraph; the logical
     indices are the static input"""
 
-    def __init__(self, scorer, indices):
+    def __init__(self, scorer, indices, same=None):
         self.static_idx = indices.clone()
         self._stream = torch.cuda.Stream(device=indices.device)
         self.graph = torch.cuda.CUDAGraph()
         torch.cuda.synchronize()
         with torch.no_grad(), torch.cuda.graph(self.graph, stream=self._stream, capture_error_mode="thread_local"):
-            self.y_pred = scorer._score_rows_eager(self.static_idx)
+            self.y_pred = scorer._score_rows_eager(self.static_idx, same=same)
 
     def run(self, indices):
         if indices.data_ptr() != self.static_idx.data_ptr():
@@ -630,6 +696,8 @@ class OnlineScorer:
         self._graphs = {}              # key -> [eager requests seen, _RequestGraph | False | None]
         self._bucket_graphs = {}       # score_requests: (bucket, ...) -> [eager calls seen, _BucketGraph | False | None]
         self._rows_graphs = {}         # score_rows: key -> [eager calls seen, _RowsGraph | False | None]
+        self._same_graphs = {}         # score(ids, same=): key + (the columns as ascending positions,) -> [eager requests seen, _RequestGraph | False | None]
+        self._same_rows_graphs = {}    # score_rows(indices, same=): the same for _RowsGraph
         self._found = None             # relabel_where's index list (one entry per row the pool can hold), from its first call on
 
     # ------------------------------------------------------------------------------------------------------------------
@@ -640,9 +708,9 @@ class OnlineScorer:
                                    torch.zeros(B, dtype=torch.float32, device=self.device))
         return c
 
-    def _assemble(self, ids, first_row=None):
+    def _assemble(self, ids, first_row=None, same=None):
         rows, labels = self._constants(ids.shape[0])
-        _values, indices, _lens = self.index.retrieve(ids, _first_row=first_row)
+        _values, indices, _lens = self.index.retrieve(ids, _first_row=first_row, _exact=same)
         # the request is the query table, the kernel's own index output the neighbour lists; -1 keeps its numpy meaning, as offline
         if self.index.window:                                                  # ... logical positions in the ring, -1 its newest row
             return ops.batch_assemble_ring(ids, labels, self.pool_ids, self.pool_labels, indices, rows, self.index.count, lib=self._lib)
@@ -650,8 +718,8 @@ class OnlineScorer:
             return ops.batch_assemble_dev(ids, labels, self.pool_ids, self.pool_labels, indices, rows, self.index.count, lib=self._lib)
         return ops.batch_assemble(ids, labels, self.pool_ids, self.pool_labels, indices, rows, lib=self._lib)
 
-    def _score_eager(self, ids, first_row=None):
-        y_pred, _loss, _reg, _saved = self.model._run_forward(self._assemble(ids, first_row), save=False, with_reg=False)
+    def _score_eager(self, ids, first_row=None, same=None):
+        y_pred, _loss, _reg, _saved = self.model._run_forward(self._assemble(ids, first_row, same), save=False, with_reg=False)
         return y_pred.reshape(-1)
 
     def append(self, rows):
@@ -739,15 +807,33 @@ class OnlineScorer:
             self.delete(found)
         return int(found.numel())
 
-    def batch(self, ids):
-        """-> data.DeviceBatch (idx [B, 1 + K, L], label_ids [B, 1 + K], y_true = zeros): what the model's forward consumes"""
-        return DeviceBatch(*self._assemble(_as_device_ids(ids, self.device)))
+    def _same_key(self, same):
+        """``same`` as the caller gave it -> its positions inside the used columns, ascending (validated here, once, as
+        ``RetrievalIndex.retrieve`` validates it: ValueError before anything is launched), or None.  The internal calls below pass
+        that tuple on; it is also what the ``same=`` graphs are keyed by, so the order the caller names the columns in costs no
+        second graph."""
+        if same is None or isinstance(same, _Exact):
+            return same
+        return _Exact(_same_positions(same, self.index._col_list))
 
-    def score(self, ids):
+    def batch(self, ids, same=None):
+        """-> data.DeviceBatch (idx [B, 1 + K, L], label_ids [B, 1 + K], y_true = zeros): what the model's forward consumes.
+        ``same``: the neighbours of a row are taken only from pool rows equal to it on those columns (``RetrievalIndex.retrieve``)."""
+        return DeviceBatch(*self._assemble(_as_device_ids(ids, self.device), same=self._same_key(same)))
+
+    def score(self, ids, same=None):
+        """fp32 [B] predictions for the encoded rows ``ids``.  ``same`` (column numbers of the encoded row, among the used columns):
+        every row's neighbours come only from pool rows that equal it on those columns — this user's history instead of anyone's
+        traffic, from the same resident pool.  With ``graph=True`` the chain of a (size, ``same``) pair is captured after
+        ``graph_warmup`` eager calls, in a dictionary of its own; the ``same=None`` graphs are not touched."""
         if self.model.training:
             raise RuntimeError("OnlineScorer.score needs the model in eval mode (model.eval())")
+        same = self._same_key(same)
         ids = _as_device_ids(ids, self.device)
         with torch.no_grad():
+            if same is not None:
+                g = self._same_graph_for(ids, same)
+                return g.run(ids) if g is not None else self._score_eager(ids, same=same)
             g = self._graph_for(ids)
             return g.run(ids) if g is not None else self._score_eager(ids)
 
@@ -768,12 +854,12 @@ class OnlineScorer:
             raise ValueError("%s: empty list of rows" % what)
         return idx
 
-    def _assemble_rows(self, idx):
+    def _assemble_rows(self, idx, same=None):
         """idx int64 [B] (device) -> (idx, label_ids, y_true) of the rows at those logical positions, each with the neighbours it had
         when it arrived: horizon = its own position.  Nothing is read back between the launches."""
         form = self.index._pool_form()
         ids, labels, before = ops.pool_gather_rows(self.pool_ids, self.pool_labels, idx, lib=self._lib, **form)
-        _values, nbr, _lens = self.index.retrieve(ids, before=before)
+        _values, nbr, _lens = self.index.retrieve(ids, before=before, _exact=same)
         # a -1 padding is the newest row the query may see, not the pool's newest row (which the assembly would take for it)
         nbr = torch.where(nbr < 0, (before - 1).clamp_(min=0).unsqueeze(1), nbr)
         rows, _zeros = self._constants(idx.numel())
@@ -783,39 +869,81 @@ class OnlineScorer:
             return ops.batch_assemble_dev(ids, labels, self.pool_ids, self.pool_labels, nbr, rows, self.index.count, lib=self._lib)
         return ops.batch_assemble(ids, labels, self.pool_ids, self.pool_labels, nbr, rows, lib=self._lib)
 
-    def _score_rows_eager(self, idx):
-        y_pred, _loss, _reg, _saved = self.model._run_forward(self._assemble_rows(idx), save=False, with_reg=False)
+    def _score_rows_eager(self, idx, same=None):
+        y_pred, _loss, _reg, _saved = self.model._run_forward(self._assemble_rows(idx, same), save=False, with_reg=False)
         return y_pred.reshape(-1)
 
-    def batch_rows(self, indices):
+    def batch_rows(self, indices, same=None):
         """-> data.DeviceBatch of the live rows at the logical positions ``indices``: ``idx[:, 0]`` their ids, ``y_true`` their REAL
         labels (the batch can go straight into ``model.train_step``), and as neighbours of row i only rows OLDER than i — the scan
         runs with the row's own position as its horizon, so the row never retrieves itself or anything that arrived after it.  A
         ``-1`` padding resolves to row ``max(i - 1, 0)``, the newest row i may see (row 0, which has nobody before it, pads with
-        itself).  The IDF weights are those of the whole live pool as it stands."""
-        return DeviceBatch(*self._assemble_rows(self._row_indices(indices, "batch_rows")))
+        itself).  The IDF weights are those of the whole live pool as it stands.  ``same``: only OLDER rows equal to row i on those columns
+        (the same user's earlier rows) are its candidates, as ``RetrievalIndex.retrieve(ids, before=, same=)`` defines them."""
+        same = self._same_key(same)
+        return DeviceBatch(*self._assemble_rows(self._row_indices(indices, "batch_rows"), same))
 
-    def score_rows(self, indices):
+    def score_rows(self, indices, same=None):
         """fp32 [B] predictions for the live rows at ``indices``, each scored against the rows older than it (``batch_rows``).  With
         ``graph=True`` and device indices, the chain of a size (<= ``graph_max_batch``) is captured after ``graph_warmup`` eager calls
         and replayed with the indices as its static input; it reads the header, the labels and the weights at replay time."""
         if self.model.training:
             raise RuntimeError("OnlineScorer.score_rows needs the model in eval mode (model.eval())")
+        same = self._same_key(same)
         given_on_device = torch.is_tensor(indices) and indices.is_cuda
         idx = self._row_indices(indices, "score_rows")
         with torch.no_grad():
+            if same is not None:                                               # (``same``: as ``batch_rows``; graphs of its own)
+                g = self._same_rows_graph_for(idx, same) if given_on_device else None
+                return g.run(idx) if g is not None else self._score_rows_eager(idx, same)
             g = self._rows_graph_for(idx) if given_on_device else None
             return g.run(idx) if g is not None else self._score_rows_eager(idx)
 
-    def evaluate_rows(self, indices):
+    def evaluate_rows(self, indices, same=None):
         """{"logloss": ..., "AUC": ...} of ``score_rows(indices)`` against the rows' stored labels (``metrics.evaluate_metrics`` on the
         host, after one device-to-host copy of predictions and labels): how well the model does on the traffic in the window"""
         from .metrics import evaluate_metrics
+        same = self._same_key(same)
         idx = self._row_indices(indices, "evaluate_rows")
-        y_pred = self.score_rows(idx)
+        y_pred = self.score_rows(idx, same=same)
         _ids, labels, _before = ops.pool_gather_rows(self.pool_ids, self.pool_labels, idx, lib=self._lib, **self.index._pool_form())
         both = torch.stack([y_pred, labels]).cpu().numpy()
         return evaluate_metrics(both[1].astype(np.float64), both[0].astype(np.float64), ["logloss", "AUC"])
+
+    def _same_graph_for(self, ids, same):
+        """``_graph_for`` for ``score(ids, same=)``: a dictionary of its own, the key extended by the columns"""
+        B = ids.shape[0]
+        if not (self.graph and ids.is_cuda and B <= self.graph_max_batch):
+            return None
+        key = (B, self.model._eval_graph_key((B, self.index.topK + 1, ids.shape[1])), same)
+        return self._captured(self._same_graphs, key, lambda: _RequestGraph(self, ids, same), "the online request with same=")
+
+    def _same_rows_graph_for(self, idx, same):
+        """``_rows_graph_for`` for ``score_rows(indices, same=)``"""
+        B = idx.numel()
+        if not (self.graph and idx.is_cuda and B <= self.graph_max_batch):
+            return None
+        key = (B, self.model._eval_graph_key((B, self.index.topK + 1, self.index.row_len)), same)
+        return self._captured(self._same_rows_graphs, key, lambda: _RowsGraph(self, idx, same), "the pool-row scoring with same=")
+
+    def _captured(self, graphs, key, capture, what):
+        """the warm-up count and the capture of one entry of a ``same=`` dictionary (at most ``graph_sizes`` entries each)"""
+        entry = graphs.get(key)
+        if entry is None:
+            if len(graphs) >= self.graph_sizes:
+                return None
+            entry = graphs[key] = [0, None]
+        if entry[1] is None:
+            entry[0] += 1
+            if entry[0] <= self.graph_warmup:
+                return None
+            try:
+                entry[1] = capture()
+            except Exception as exc:
+                import logging
+                logging.warning("hipGraph capture of %s failed (%s: %s); continuing with eager launches", what, type(exc).__name__, exc)
+                entry[1] = False
+        return entry[1] or None
 
     def _rows_graph_for(self, idx):
         B = idx.numel()

@@ -1205,3 +1205,61 @@ def bm25_topk_split_before(db_t, qry_ids, qry_idf, before, topk, header=None, ri
     lib.call("rat_bm25_topk_split_before", _p(db_t), form, _p(header), n_rows, capacity, _p(qry_ids), _p(qry_idf), _p(before), _p(out_v),
              _p(out_i), _p(out_l), _p(ws), ws.numel() * 8, Q, F, int(topk), int(splits), _stream(db_t))
     return out_v, out_i, out_l
+
+
+# ----------------------------------------------------------------------------- neighbours equal on given columns (rat_amd/online.py)
+BM25_EXACT_AUTO_GROUPS = 256                           # RAT_BM25_EXACT_AUTO_GROUPS
+
+
+def bm25_exact_count(db_t, ids, cols, exact_mask, before=None, header=None, ring=False, n_rows=None, groups=0, lib=None):
+    """-> counts int64 [Q], on the device: for every row of ids int32 [Q, L] the number of live rows of db_t int32 [F, capacity] (below
+    before[q], int64 [Q], when given) that equal it on every used column whose bit is set in `exact_mask` (bit f = used column f =
+    column cols[f] of ids).  The pool's form as in _pool_form; groups = 0: the number of row ranges is chosen from the capacity."""
+    lib = lib or get_lib()
+    _chk(db_t, torch.int32, "db_t"), _chk(ids, torch.int32, "ids"), _chk(cols, torch.int32, "cols"), _chk(before, torch.int64, "before")
+    F, capacity = db_t.shape
+    Q, L = ids.shape
+    assert cols.numel() == F and (before is None or (before.ndim == 1 and before.numel() == Q))
+    form, n_rows = _pool_form(header, ring, n_rows, capacity)
+    dev = db_t.device
+    counts = torch.empty((Q,), dtype=torch.int64, device=dev)
+    ws = torch.empty(Q * (int(groups) or BM25_EXACT_AUTO_GROUPS), dtype=torch.int64, device=dev)
+    lib.call("rat_bm25_exact_count", _p(db_t), form, _p(header), n_rows, capacity, _p(ids), _p(cols), int(exact_mask), _p(before),
+             _p(counts), _p(ws), ws.numel() * 8, Q, L, F, int(groups), _stream(db_t))
+    return counts
+
+
+def bm25_exact_plan(counts, topk, lib=None):
+    """counts int64 [Q] (device) -> (first_row int64 [Q]: the first query with a candidate, for every query, 0 when there is none — what
+    bm25_query_prepare takes as ``first_row``; listing int32 [1]: 1 when no count exceeds topk), on the device"""
+    lib = lib or get_lib()
+    _chk(counts, torch.int64, "counts")
+    Q = counts.numel()
+    first_row = torch.empty((Q,), dtype=torch.int64, device=counts.device)
+    listing = torch.empty((1,), dtype=torch.int32, device=counts.device)
+    lib.call("rat_bm25_exact_plan", _p(counts), _p(first_row), _p(listing), Q, int(topk), _stream(counts))
+    return first_row, listing
+
+
+def bm25_topk_split_exact(db_t, qry_ids, qry_idf, exact_mask, listing, topk, before=None, header=None, ring=False, n_rows=None, splits=0,
+                          lib=None):
+    """bm25_topk_split_before whose candidates are the rows equal to the query on the used columns in `exact_mask`: a candidate scores
+    (the weights of the other columns it matches) + 1, anything else 0; listing int32 [1] (device) != 0: each query's entries in
+    ascending index with value 1.0 instead.  before (int64 [Q], device) may be None.  The pool's form as in _pool_form."""
+    lib = lib or get_lib()
+    _chk(db_t, torch.int32, "db_t"), _chk(qry_ids, torch.int32, "qry_ids"), _chk(qry_idf, torch.float64, "qry_idf")
+    _chk(before, torch.int64, "before"), _chk(listing, torch.int32, "listing")
+    F, capacity = db_t.shape
+    Q = qry_ids.shape[0]
+    assert tuple(qry_ids.shape) == (Q, F) and tuple(qry_idf.shape) == (Q, F) and listing.numel() >= 1
+    assert before is None or (before.ndim == 1 and before.numel() == Q)
+    form, n_rows = _pool_form(header, ring, n_rows, capacity)
+    dev = db_t.device
+    nbytes = lib.size("rat_bm25_topk_split_workspace", Q, int(topk), int(splits))
+    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    out_v = torch.empty((Q, topk), dtype=torch.float64, device=dev)
+    out_i = torch.empty((Q, topk), dtype=torch.int64, device=dev)
+    out_l = torch.empty((Q,), dtype=torch.int64, device=dev)
+    lib.call("rat_bm25_topk_split_exact", _p(db_t), form, _p(header), n_rows, capacity, _p(qry_ids), _p(qry_idf), int(exact_mask),
+             _p(before), _p(listing), _p(out_v), _p(out_i), _p(out_l), _p(ws), ws.numel() * 8, Q, F, int(topk), int(splits), _stream(db_t))
+    return out_v, out_i, out_l
