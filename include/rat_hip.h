@@ -817,6 +817,25 @@ int rat_ffn_bwd_drop(const float* x, const float* dy, float* dx, const float* w1
 int rat_dropout_dev(const float* x, float* y, int64_t n, float p, const uint64_t* seed_dev, void* stream);
 int rat_dropout_seeds(uint64_t* seeds_dev, int n, uint64_t base_seed, uint64_t* counter_dev, void* stream);
 
+/* Evaluation metrics on the device (csrc/metrics.hip): logloss, AUC and the per-group GAUC of n predictions, replacing the reference's
+ * host pass (fuxictr/metrics.py:22-41: sklearn log_loss / roc_auc_score over numpy copies; GAUC, fuxictr/metrics.py:29-39, is `pass`
+ * there).  y_pred, y_true: fp32 [n]; group: int32 [n] or NULL (no GAUC) — any int32 is a legal group id, it is a sort key only.
+ * 1 <= n <= 2^31 - 1.  The caller owns every buffer; nothing is allocated, synchronised or read back.
+ *   out (float64 [8], device): [0] logloss = mean of -(y log p + (1 - y) log(1 - p)) in float64, p = clip(double(pred), 1e-7, 1 - 1e-7),
+ *       summed over fixed 1024-row tiles in index order (independent of scheduling);
+ *   [1] AUC = U2 / (2 pos neg), U2 = sum over runs of equal predictions, ascending, of pos_run (2 neg_before_run + neg_run) in int64
+ *       (-0.0 ties with +0.0; pos means y_true == 1): exact, one division;
+ *   [2] GAUC = sum_g n_g AUC_g / sum_g n_g over the groups that hold both classes, n_g = rows of group g (the definition later FuxiCTR
+ *       releases use), summed in ascending group order through a fixed tree: independent of the order of the rows; NaN when group == NULL;
+ *   [3] n_pos  [4] n_neg  [5] groups counted  [6] rows in the counted groups
+ *   [7] status bits: 1 a prediction is NaN (logloss, AUC, GAUC = NaN), 2 a label is neither 0 nor 1 (AUC, GAUC = NaN), 4 only one class
+ *       present (AUC, GAUC = NaN), 8 groups given and none holds both classes (GAUC = NaN).
+ * workspace: rat_eval_metrics_workspace(n, group != NULL) bytes, 256-byte aligned.  -1 + rat_last_error() on a null pointer, n out of
+ * range, a workspace too small or misaligned; nothing is launched then. */
+size_t rat_eval_metrics_workspace(int64_t n, int grouped);
+int rat_eval_metrics(const float* y_pred, const float* y_true, const int32_t* group, int64_t n, double* out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

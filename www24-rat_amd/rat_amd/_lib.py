@@ -181,6 +181,9 @@ _SIGNATURES = {
     "rat_bm25_exact_plan": (c_int, [_P, _P, _P, c_int64, c_int, _P]),
     "rat_bm25_topk_split_exact": (c_int, [_P, c_int, _P, c_int64, c_int64, _P, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, c_size_t,
                                           c_int64, c_int, c_int, c_int, _P]),
+    # evaluation metrics on the device: logloss, AUC and per-group GAUC of a prediction vector -> float64 [8]
+    "rat_eval_metrics_workspace": (c_size_t, [c_int64, c_int]),
+    "rat_eval_metrics": (c_int, [_P, _P, _P, c_int64, _P, _P, c_size_t, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from .metrics import device_metrics as evaluate_metrics_on_device
 from .metrics import evaluate_metrics
 
 
@@ -56,7 +57,9 @@ class BaseModel(nn.Module):
     def __init__(self, feature_map, model_id="BaseModel", gpu=-1, monitor="AUC", save_best_only=True,
                  monitor_mode="max", patience=2, every_x_epochs=1, embedding_regularizer=None, net_regularizer=None,
                  reduce_lr_on_plateau=True, embedding_initializer="torch.nn.init.normal_(std=1e-4)",
-                 retrieval_augmented=False, retrieval_configs=None, **kwargs):
+                 retrieval_augmented=False, retrieval_configs=None, device_metrics=False, group_id=None, **kwargs):
+        """device_metrics: evaluate_generator computes its metrics on the device (metrics.device_metrics: 64 bytes come back instead of
+        every prediction and label).  group_id: the categorical feature whose id on the target row groups the rows for "GAUC"."""
         super().__init__()
         self.device = get_device(gpu)
         self._monitor = Monitor(kv=monitor)
@@ -78,6 +81,19 @@ class BaseModel(nn.Module):
         self.model_dir = os.path.join(kwargs["model_root"], feature_map.dataset_id)
         self.checkpoint = os.path.abspath(os.path.join(self.model_dir, self.model_id + ".model"))
         self._validation_metrics = kwargs["metrics"]
+        self._device_metrics = bool(device_metrics)
+        self._group_id, self._group_col = group_id, None
+        if group_id is not None:
+            spec = feature_map.feature_specs.get(group_id)
+            if spec is None:
+                raise ValueError("group_id=%r is not a feature of this dataset" % (group_id,))
+            if spec["type"] != "categorical":
+                raise ValueError("group_id=%r is a %s field: GAUC groups by one id per row, so it takes a plain categorical field"
+                                 % (group_id, spec["type"]))
+            self._group_col = int(spec["index"])
+        if "GAUC" in (self._validation_metrics or []) and group_id is None:
+            raise ValueError('metrics holds "GAUC" but no group_id names the feature to group by')
+        self._refuse_new_eval_options_under_dp()
         self._verbose = kwargs["verbose"]
         self._max_gradient_norm = 10.0
 
@@ -304,6 +320,8 @@ class BaseModel(nn.Module):
         """base_model.py:232-247.  Under data parallelism (and a batch source that can shard: rat_amd.data) each rank runs the forward
         on its slice of every batch — nothing is dropped — and all ranks compute the metrics from the all-gathered predictions, so they
         agree on early stopping / lr decay by construction."""
+        if self._device_metrics or self._group_col is not None:
+            return self._evaluate_generator_options(data_generator)
         self.eval()
         preds, trues = [], []
         world = self._world_size()
@@ -346,8 +364,40 @@ class BaseModel(nn.Module):
         dist.all_gather(parts, mine)
         return tuple(torch.cat([parts[r][i, :counts[r]] for r in range(world)]) for i in range(len(vectors)))
 
-    def evaluate_metrics(self, y_true, y_pred, metrics):
-        return evaluate_metrics(y_true, y_pred, metrics)
+    def evaluate_metrics(self, y_true, y_pred, metrics, group_index=None):
+        return evaluate_metrics(y_true, y_pred, metrics, group_index=group_index)
+
+    def _refuse_new_eval_options_under_dp(self):
+        if (self._device_metrics or self._group_id is not None) and self._dp():
+            raise ValueError("device_metrics / group_id are not available under data parallelism: the ranks evaluate shards of every "
+                             "batch and all-gather predictions and labels only — neither the metric chain nor the group ids are "
+                             "exchanged.  Evaluate on one device, or drop the two options")
+
+    def _evaluate_generator_options(self, data_generator):
+        """evaluate_generator with device_metrics and / or group_id: predictions, labels and (for "GAUC") the target rows' ids of the
+        group column stay on the device.  With device_metrics the metric chain runs there and 64 bytes come back; without, the three
+        vectors are copied once and metrics.evaluate_metrics runs on the host as before."""
+        self._refuse_new_eval_options_under_dp()
+        self.eval()
+        metrics = self._validation_metrics
+        col = self._group_col if "GAUC" in metrics else None
+        preds, trues, groups = [], [], []
+        with torch.no_grad():
+            for batch_data in data_generator:
+                out = self.forward(batch_data)
+                preds.append(out["y_pred"].reshape(-1))
+                trues.append(out["y_true"].reshape(-1))
+                if col is not None:
+                    ids = batch_data.idx if hasattr(batch_data, "idx") else batch_data[0]      # DeviceBatch or the 4-tuple
+                    groups.append(ids[:, 0, col].to(self.device, torch.int32).clone())
+        empty = torch.zeros((0,), dtype=torch.float32, device=self.device)
+        y_pred, y_true = torch.cat(preds or [empty]), torch.cat(trues or [empty])
+        group = torch.cat(groups or [empty.to(torch.int32)]) if col is not None else None
+        self.check_id_errors()
+        if self._device_metrics:
+            return evaluate_metrics_on_device(y_true, y_pred, metrics, group_index=group, lib=getattr(self, "_lib", None))
+        return self.evaluate_metrics(y_true.double().cpu().numpy(), y_pred.double().cpu().numpy(), metrics,
+                                     group_index=None if group is None else group.cpu().numpy())
 
     def predict_generator(self, data_generator):
         """base_model.py:252-273."""

@@ -899,16 +899,45 @@ class OnlineScorer:
             g = self._rows_graph_for(idx) if given_on_device else None
             return g.run(idx) if g is not None else self._score_rows_eager(idx)
 
-    def evaluate_rows(self, indices, same=None):
-        """{"logloss": ..., "AUC": ...} of ``score_rows(indices)`` against the rows' stored labels (``metrics.evaluate_metrics`` on the
-        host, after one device-to-host copy of predictions and labels): how well the model does on the traffic in the window"""
-        from .metrics import evaluate_metrics
+    def _group_column(self, group):
+        """``group``: None, or the index of one id column of the pool's rows -> that index, checked"""
+        if group is None:
+            return None
+        L = int(self.pool_ids.shape[1])
+        if isinstance(group, bool) or not isinstance(group, (int, np.integer)):
+            raise ValueError("group takes the index of one id column of the rows, got %r" % (group,))
+        if not 0 <= int(group) < L:
+            raise ValueError("group=%d is not an id column of the rows (they hold %d)" % (int(group), L))
+        return int(group)
+
+    def _rows_vectors(self, indices, same, group, what):
+        """-> (y_pred fp32 [B], labels fp32 [B], group ids int32 [B] or None) of the live rows at ``indices``, on the device"""
         same = self._same_key(same)
-        idx = self._row_indices(indices, "evaluate_rows")
+        col = self._group_column(group)
+        idx = self._row_indices(indices, what)
         y_pred = self.score_rows(idx, same=same)
-        _ids, labels, _before = ops.pool_gather_rows(self.pool_ids, self.pool_labels, idx, lib=self._lib, **self.index._pool_form())
+        ids, labels, _before = ops.pool_gather_rows(self.pool_ids, self.pool_labels, idx, lib=self._lib, **self.index._pool_form())
+        return y_pred, labels, (None if col is None else ids[:, col].contiguous())
+
+    def evaluate_rows(self, indices, same=None, group=None, device=False):
+        """{"logloss": ..., "AUC": ...} of ``score_rows(indices)`` against the rows' stored labels: how well the model does on the
+        traffic in the window.  ``group=col`` (the index of one id column of the rows, e.g. the user's) adds "GAUC": the per-group AUC
+        weighted by the groups' rows.  By default ``metrics.evaluate_metrics`` runs on the host after one device-to-host copy of the
+        vectors; ``device=True`` runs the metric chain on the device (``metrics.device_metrics``) and copies 64 bytes."""
+        from .metrics import device_metrics, evaluate_metrics
+        y_pred, labels, gids = self._rows_vectors(indices, same, group, "evaluate_rows")
+        names = ["logloss", "AUC"] + (["GAUC"] if gids is not None else [])
+        if device:
+            return device_metrics(labels, y_pred, names, group_index=gids, lib=self._lib)
         both = torch.stack([y_pred, labels]).cpu().numpy()
-        return evaluate_metrics(both[1].astype(np.float64), both[0].astype(np.float64), ["logloss", "AUC"])
+        return evaluate_metrics(both[1].astype(np.float64), both[0].astype(np.float64), names,
+                                group_index=None if gids is None else gids.cpu().numpy())
+
+    def metrics_rows(self, indices, same=None, group=None):
+        """the raw float64 [8] device tensor of ``ops.eval_metrics`` over ``score_rows(indices)`` and the rows' stored labels (logloss, AUC,
+        GAUC — NaN without ``group`` —, n_pos, n_neg, groups counted, their rows, status bits): nothing is read back, a monitor can collect many of them and copy once"""
+        y_pred, labels, gids = self._rows_vectors(indices, same, group, "metrics_rows")
+        return ops.eval_metrics(y_pred.contiguous(), labels, gids, lib=self._lib)
 
     def _same_graph_for(self, ids, same):
         """``_graph_for`` for ``score(ids, same=)``: a dictionary of its own, the key extended by the columns"""

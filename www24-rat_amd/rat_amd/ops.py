@@ -1263,3 +1263,26 @@ def bm25_topk_split_exact(db_t, qry_ids, qry_idf, exact_mask, listing, topk, bef
     lib.call("rat_bm25_topk_split_exact", _p(db_t), form, _p(header), n_rows, capacity, _p(qry_ids), _p(qry_idf), int(exact_mask),
              _p(before), _p(listing), _p(out_v), _p(out_i), _p(out_l), _p(ws), ws.numel() * 8, Q, F, int(topk), int(splits), _stream(db_t))
     return out_v, out_i, out_l
+
+
+# ----------------------------------------------------------------------------- evaluation metrics on the device (rat_amd/metrics.py)
+def eval_metrics(y_pred, y_true, group=None, lib=None):
+    """-> float64 [8] on the inputs' device, nothing read back: {logloss, AUC, GAUC, n_pos, n_neg, groups counted, rows in the counted
+    groups, status bits} (include/rat_hip.h: rat_eval_metrics) of y_pred fp32 [n] against y_true fp32 [n]; group int32 [n] or None
+    (then GAUC is NaN).  Status bits: 1 a NaN prediction, 2 a label that is neither 0 nor 1, 4 one class only, 8 no group holds both
+    classes — the metric a bit concerns is NaN."""
+    lib = lib or get_lib()
+    _chk(y_pred, name="y_pred"), _chk(y_true, name="y_true"), _chk(group, torch.int32, "group")
+    n = y_pred.numel()
+    if y_pred.ndim != 1 or tuple(y_true.shape) != (n,) or (group is not None and tuple(group.shape) != (n,)):
+        raise ValueError("eval_metrics takes 1-D vectors of one length")
+    dev = y_pred.device
+    if y_true.device != dev or (group is not None and group.device != dev):
+        raise ValueError("eval_metrics: the vectors sit on different devices")
+    nbytes = lib.size("rat_eval_metrics_workspace", n, 0 if group is None else 1)
+    ws = torch.empty((nbytes + 255) // 8 + 32, dtype=torch.int64, device=dev)
+    skip = (-ws.data_ptr() % 256) // 8                                           # the C ABI wants 256-byte alignment
+    ws = ws[skip:]
+    out = torch.empty(8, dtype=torch.float64, device=dev)
+    lib.call("rat_eval_metrics", _p(y_pred), _p(y_true), _p(group), n, _p(out), _p(ws), nbytes, _stream(y_pred))
+    return out
