@@ -6,7 +6,12 @@ prove on real hardware; RCCL itself only runs in the driver's scaling job.
 
 Checked: the two replicas stay bit-identical, and after five steps they hold what ONE process holds after five steps on the full
 batch (2e-4, the tolerance of tests/test_dp_gloo.py) — once with the table gradients as all-gathered row lists, once as the dense
-all-reduce."""
+all-reduce.
+
+This is an end-to-end check at one small shape.  Kernel-level parity of the kernels this path adds — SyncBN (rat_bn_local_stats,
+rat_bn_relu_fwd_sync, rat_bn_bwd_local_sums, rat_bn_relu_bwd_sync) and the owner-partitioned exchange (rat_owner_counts / _pack /
+_unpack / _scatter), worlds up to 8, ragged shards, the sizes past the grid caps — lives in tests/dp_cases.py, run by
+tests/test_gpu_dp_kernels.py here and by tests/test_dp_kernels.py on the emulator."""
 import os
 import subprocess
 import sys
