@@ -63,7 +63,7 @@ def check_split_dev(device, lib, capacity=1200, ns=(1, 255, 256, 1000, None), sp
                 whole = oc.single_range_topk(lib, db_t, q_ids, q_idf, topk)
                 poison_would_win |= bool((whole[1] >= n).any())
             for s in splits + (0,):
-                got = ops.bm25_topk_split_dev(db_t, _count(n, device), q_ids, q_idf, topk, splits=s, lib=lib)
+                got = ops.bm25_topk_split(db_t, q_ids, q_idf, topk, splits=s, header=_count(n, device), lib=lib)
                 oc.assert_bitwise(got, want, "n=%d K=%d splits=%d" % (n, topk, s))
     assert poison_would_win, "the rows beyond n would not have been retrieved anyway: the test shows nothing"
 
@@ -89,7 +89,7 @@ def check_split_dev_ties(device, lib, capacity=1500):
         for s in (2, 3, 4):
             chunk = -(-n // s)
             assert len({r // chunk for r in (0, 256, 512)}) >= 2
-            got = ops.bm25_topk_split_dev(db_t, _count(n, device), q_ids, q_idf, topk, splits=s, lib=lib)
+            got = ops.bm25_topk_split(db_t, q_ids, q_idf, topk, splits=s, header=_count(n, device), lib=lib)
             oc.assert_bitwise(got, want, "ties K=%d splits=%d" % (topk, s))
 
 
@@ -105,7 +105,7 @@ def check_split_dev_after_append(device, lib, capacity=700, n=300, M=70):
     q_ids, q_idf = _up(qry.astype(np.int32), device), _up(w, device)
     db_t, count, cols = _up(db.astype(np.int32).T, device), _count(n, device), _up(np.array([2, 0, 1], dtype=np.int32), device)
     topk = 5
-    before = ops.bm25_topk_split_dev(db_t, count, q_ids, q_idf, topk, splits=3, lib=lib)
+    before = ops.bm25_topk_split(db_t, q_ids, q_idf, topk, splits=3, header=count, lib=lib)
     oc.assert_bitwise(before, oc.single_range_topk(lib, _up(db[:n].astype(np.int32).T, device), q_ids, q_idf, topk), "before")
     new = np.repeat(qry[:1], M, axis=0)                                    # [M, 3] in pool-column order
     wide = np.zeros((M, 4), dtype=np.int32)                                # encoded rows of 4 ids: pool column f is row column cols[f]
@@ -114,7 +114,7 @@ def check_split_dev_after_append(device, lib, capacity=700, n=300, M=70):
     assert int(count.cpu()[0]) == n + M
     grown = np.concatenate([db[:n], new])
     for s in (1, 3, 64):
-        got = ops.bm25_topk_split_dev(db_t, count, q_ids, q_idf, topk, splits=s, lib=lib)
+        got = ops.bm25_topk_split(db_t, q_ids, q_idf, topk, splits=s, header=count, lib=lib)
         oc.assert_bitwise(got, oc.single_range_topk(lib, _up(grown.astype(np.int32).T, device), q_ids, q_idf, topk), "after s=%d" % s)
         assert got[1][0].cpu().tolist() == list(range(n, n + topk))        # query 0: the appended rows, lowest index first
         assert int(got[1].max()) < n + M

@@ -189,7 +189,7 @@ def check_delete_ties(device, lib, topks=(3, 9), splits=(1, 3, 0)):
             want = oc.single_range_topk(lib, db_t_live, q_ids, q_idf, topk)
             assert want[1][0][:3].tolist() == [510, 255, 698]
             for s in splits:
-                got = ops.bm25_topk_split_ring(db_t, hdr, q_ids, q_idf, topk, splits=s, lib=lib)
+                got = ops.bm25_topk_split(db_t, q_ids, q_idf, topk, splits=s, header=hdr, ring=True, lib=lib)
                 oc.assert_bitwise(got, want, "ties after delete: capacity=%d head=%d K=%d splits=%d" % (capacity, head, topk, s))
 
 

@@ -62,7 +62,7 @@ def check_ring_scan(device, lib, capacity=1200, ns=(1, 255, 1000, None), splits=
                 seen["live_rows_wrap"] |= head + n > capacity
                 db_t, hdr = _up(_rotate(logical, head).astype(np.int32).T, device), _header(n, head, device)
                 for topk in topks:
-                    got = ops.bm25_topk_split_ring(db_t, hdr, q_ids, q_idf, topk, splits=s, lib=lib)
+                    got = ops.bm25_topk_split(db_t, q_ids, q_idf, topk, splits=s, header=hdr, ring=True, lib=lib)
                     oc.assert_bitwise(got, want[topk], "n=%d head=%d K=%d splits=%d" % (n, head, topk, s))
     assert all(seen.values()), seen
 
@@ -74,13 +74,14 @@ def check_ring_scan_clamps(device, lib, capacity=300):
     base, qry, w = ac.poisoned_pool(capacity, seed=5)
     q_ids, q_idf, db_t = _up(qry.astype(np.int32), device), _up(w, device), _up(base.astype(np.int32).T, device)
     full = oc.single_range_topk(lib, db_t, q_ids, q_idf, 3)
-    oc.assert_bitwise(ops.bm25_topk_split_ring(db_t, _header(capacity + 77, -5, device), q_ids, q_idf, 3, splits=3, lib=lib), full, "over")
-    got = ops.bm25_topk_split_ring(db_t, _header(-4, 0, device), q_ids, q_idf, 3, splits=3, lib=lib)
+    oc.assert_bitwise(ops.bm25_topk_split(db_t, q_ids, q_idf, 3, splits=3, header=_header(capacity + 77, -5, device), ring=True, lib=lib),
+                      full, "over")
+    got = ops.bm25_topk_split(db_t, q_ids, q_idf, 3, splits=3, header=_header(-4, 0, device), ring=True, lib=lib)
     assert int(got[2].abs().max()) == 0 and int(got[1].max()) == -1
     last = np.roll(base, 1, axis=0)                                        # head = capacity - 1 after the clamp: slot capacity - 1 first
     want = oc.single_range_topk(lib, _up(last.astype(np.int32).T, device), q_ids, q_idf, 3)
-    oc.assert_bitwise(ops.bm25_topk_split_ring(db_t, _header(capacity, capacity + 9, device), q_ids, q_idf, 3, splits=2, lib=lib), want,
-                      "head over")
+    oc.assert_bitwise(ops.bm25_topk_split(db_t, q_ids, q_idf, 3, splits=2, header=_header(capacity, capacity + 9, device), ring=True, lib=lib),
+                      want, "head over")
 
 
 # ---- 2. ties follow age, not address -------------------------------------------------------------------------------------------------
@@ -118,7 +119,7 @@ def check_ring_ties(device, lib):
                 assert torch.equal(by_slot[0], want[0]) and not torch.equal(as_logical, want[1]), "slot order == age order: shows nothing"
                 assert as_logical[0][:2].tolist() == [512, 300]
             for s in (1, 2, 3, 4, 0):
-                got = ops.bm25_topk_split_ring(db_t, _header(n, head, device), q_ids, q_idf, topk, splits=s, lib=lib)
+                got = ops.bm25_topk_split(db_t, q_ids, q_idf, topk, splits=s, header=_header(n, head, device), ring=True, lib=lib)
                 oc.assert_bitwise(got, want, "ties capacity=%d K=%d splits=%d" % (capacity, topk, s))
 
 

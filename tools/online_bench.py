@@ -681,13 +681,8 @@ def part_rows(emit, quick):
             ids = torch.from_numpy(np.stack([rs.randint(0, v, size=Q) for v in vocab], axis=1).astype(np.int32)).to(dev)
             q_ids, q_idf = ops.bm25_query_prepare(ids, index.cols, index.table_ids, index.table_idf, index.table_offsets)
             before = torch.full((Q,), n, dtype=torch.int64, device=dev)
-            if index.window:
-                plain = lambda: ops.bm25_topk_split_ring(index.db_t, index.count, q_ids, q_idf, K)          # noqa: E731
-            elif index.capacity is not None:
-                plain = lambda: ops.bm25_topk_split_dev(index.db_t, index.count, q_ids, q_idf, K)           # noqa: E731
-            else:
-                plain = lambda: ops.bm25_topk_split(index.db_t, q_ids, q_idf, K)                            # noqa: E731
-            horizon = lambda: ops.bm25_topk_split_before(index.db_t, q_ids, q_idf, before, K, **form)        # noqa: E731
+            plain = lambda: ops.bm25_topk_split(index.db_t, q_ids, q_idf, K, **form)                         # noqa: E731
+            horizon = lambda: ops.bm25_topk_split(index.db_t, q_ids, q_idf, K, before=before, **form)        # noqa: E731
             want, got = plain(), horizon()
             torch.cuda.synchronize()
             for g, w in zip(got, want):
@@ -758,12 +753,7 @@ def part_same(emit, quick):
             first_row, _flag = ops.bm25_exact_plan(ops.bm25_exact_count(index.db_t, ids, index.cols, mask, **form), K)
             q_ids, q_idf = ops.bm25_query_prepare(ids, index.cols, index.table_ids, index.table_idf, index.table_offsets, first_row=first_row)
             p_ids, p_idf = ops.bm25_query_prepare(ids, index.cols, index.table_ids, index.table_idf, index.table_offsets)
-            if index.window:
-                plain = lambda: ops.bm25_topk_split_ring(index.db_t, index.count, p_ids, p_idf, K)          # noqa: E731
-            elif index.capacity is not None:
-                plain = lambda: ops.bm25_topk_split_dev(index.db_t, index.count, p_ids, p_idf, K)           # noqa: E731
-            else:
-                plain = lambda: ops.bm25_topk_split(index.db_t, p_ids, p_idf, K)                            # noqa: E731
+            plain = lambda: ops.bm25_topk_split(index.db_t, p_ids, p_idf, K, **form)                         # noqa: E731
 
             def chain():
                 counts = ops.bm25_exact_count(index.db_t, ids, index.cols, mask, **form)

@@ -83,6 +83,8 @@ per call, ``same=``; not built: ``same`` with ``request_offsets``, and all used 
 than 32 retrieval columns, data-parallel models.  Rows are deleted from a
 ``window=True`` pool only: the append-only form reserves its IDF tables for the rows that can still come, which deletions would undo.
 """
+import logging
+
 import numpy as np
 import torch
 
@@ -106,23 +108,37 @@ def _as_device_ids(ids, device):
     return ids.contiguous()
 
 
+_INT_DTYPES = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)
+
+
+def _device_list(t, shape, dtype, device=None, fits=lambda n: True):
+    """a DEVICE tensor of integers -> int64, contiguous (on ``device``, when given), checked by shape (1-D, and ``fits(numel)``) and
+    dtype only and passed through UNREAD: no synchronisation, the kernels clamp or skip what is out of range.  ``shape`` / ``dtype``:
+    what the ValueError says the list must be.  Anything else -> None: the caller validates it on the host"""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        return None
+    if t.ndim != 1 or not fits(t.numel()):
+        raise ValueError("%s, got shape %s" % (shape, tuple(t.shape)))
+    if t.dtype not in _INT_DTYPES:
+        raise ValueError("%s, got dtype %s" % (dtype, t.dtype))
+    return t.detach().to(device=device, dtype=torch.int64).contiguous()
+
+
 def _request_offsets(offsets, B):
     """what ``retrieve(ids, request_offsets)`` takes -> (int64 [R + 1] on the host, None) for host-side offsets, validated — 1-D,
     integer dtype, from 0 to B, strictly ascending, or ValueError — or (None, the device tensor as int64), passed through UNREAD: no
     synchronisation, and the kernel clamps what it derives from it"""
-    if torch.is_tensor(offsets) and offsets.is_cuda:
-        if offsets.ndim != 1 or offsets.numel() < 2:
-            raise ValueError("request_offsets must be a 1-D list of R + 1 row offsets, got shape %s" % (tuple(offsets.shape),))
-        if offsets.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
-            raise ValueError("request_offsets must be integers, got dtype %s" % offsets.dtype)
-        return None, offsets.detach().to(torch.int64).contiguous()
+    shape, dtype = "request_offsets must be a 1-D list of R + 1 row offsets", "request_offsets must be integers"
+    off_dev = _device_list(offsets, shape, dtype, fits=lambda n: n >= 2)
+    if off_dev is not None:
+        return None, off_dev
     if torch.is_tensor(offsets):
         offsets = offsets.detach().numpy()
     off = np.asarray(offsets)
     if off.ndim != 1 or off.size < 2:
-        raise ValueError("request_offsets must be a 1-D list of R + 1 row offsets, got shape %s" % (tuple(off.shape),))
+        raise ValueError("%s, got shape %s" % (shape, tuple(off.shape)))
     if not np.issubdtype(off.dtype, np.integer):
-        raise ValueError("request_offsets must be integers, got dtype %s" % off.dtype)
+        raise ValueError("%s, got dtype %s" % (dtype, off.dtype))
     off = off.astype(np.int64)
     if off[0] != 0:
         raise ValueError("request_offsets must start at 0, got %d" % off[0])
@@ -194,8 +210,9 @@ def _key_table(cols, keys, where, what):
     return np.asarray([where[x] for x in c], dtype=np.int32), np.ascontiguousarray(k)
 
 
-def _row_list(indices, n, what):
-    """host-side logical row indices -> int64 [m] in the caller's order, or ValueError: integer dtype, inside [0, n), no duplicates"""
+def _row_list(indices, n, what, rows="pool", distinct=True):
+    """host-side logical row indices -> int64 [m] in the caller's order, or ValueError: integer dtype, inside [0, n) — the live rows of
+    the ``rows`` —, no duplicates (``distinct=False``: left to the caller)"""
     if torch.is_tensor(indices):
         indices = indices.detach().cpu().numpy()
     idx = np.atleast_1d(np.asarray(indices))
@@ -206,32 +223,28 @@ def _row_list(indices, n, what):
     if not np.issubdtype(idx.dtype, np.integer):
         raise ValueError("%s takes integer row indices, got dtype %s" % (what, idx.dtype))
     if idx.min() < 0 or idx.max() >= n:
-        raise ValueError("%s: index outside [0, %d), the live rows of the pool (a negative index does not count from the end)" % (what, n))
+        raise ValueError("%s: index outside [0, %d), the live rows of the %s (a negative index does not count from the end)"
+                         % (what, n, rows))
     idx = idx.astype(np.int64)
-    if len(np.unique(idx)) != len(idx):
+    if distinct and len(np.unique(idx)) != len(idx):
         raise ValueError("%s: duplicate index" % what)
     return np.ascontiguousarray(idx)
-
-
-_INT_DTYPES = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)
 
 
 def _before_list(before, B, device):
     """what ``retrieve(ids, before=...)`` takes -> int64 [B] on the device.  A host array is validated — 1-D, integer dtype, B entries,
     or ValueError — and uploaded; a device tensor is checked by shape and dtype only and passed through UNREAD (the kernel clamps)"""
-    if torch.is_tensor(before) and before.is_cuda:
-        if before.ndim != 1 or before.numel() != B:
-            raise ValueError("before must be a 1-D list of %d horizons (one per row), got shape %s" % (B, tuple(before.shape)))
-        if before.dtype not in _INT_DTYPES:
-            raise ValueError("before must be integers, got dtype %s" % before.dtype)
-        return before.detach().to(device, torch.int64).contiguous()
+    shape, dtype = "before must be a 1-D list of %d horizons (one per row)" % B, "before must be integers"
+    on_device = _device_list(before, shape, dtype, device, fits=lambda n: n == B)
+    if on_device is not None:
+        return on_device
     if torch.is_tensor(before):
         before = before.detach().numpy()
     b = np.asarray(before)
     if b.ndim != 1 or b.size != B:
-        raise ValueError("before must be a 1-D list of %d horizons (one per row), got shape %s" % (B, tuple(b.shape)))
+        raise ValueError("%s, got shape %s" % (shape, tuple(b.shape)))
     if not np.issubdtype(b.dtype, np.integer):
-        raise ValueError("before must be integers, got dtype %s" % b.dtype)
+        raise ValueError("%s, got dtype %s" % (dtype, b.dtype))
     return torch.from_numpy(np.ascontiguousarray(b.astype(np.int64))).to(device, non_blocking=True)
 
 
@@ -358,14 +371,8 @@ class RetrievalIndex:
             return self._retrieve_same(ids, before, sum(1 << f for f in exact))
         qry_ids, qry_idf = ops.bm25_query_prepare(ids, self.cols, self.table_ids, self.table_idf, self.table_offsets,
                                                   first_row=_first_row, lib=self._lib)
-        if before is not None:
-            return ops.bm25_topk_split_before(self.db_t, qry_ids, qry_idf, before, self.topK, splits=self.splits, lib=self._lib,
-                                              **self._pool_form())
-        if self.window:
-            return ops.bm25_topk_split_ring(self.db_t, self.count, qry_ids, qry_idf, self.topK, splits=self.splits, lib=self._lib)
-        if self.capacity is not None:
-            return ops.bm25_topk_split_dev(self.db_t, self.count, qry_ids, qry_idf, self.topK, splits=self.splits, lib=self._lib)
-        return ops.bm25_topk_split(self.db_t, qry_ids, qry_idf, self.topK, splits=self.splits, lib=self._lib)
+        return ops.bm25_topk_split(self.db_t, qry_ids, qry_idf, self.topK, splits=self.splits, before=before, lib=self._lib,
+                                   **self._pool_form())
 
     def _retrieve_same(self, ids, before, mask):
         """count -> plan -> prepare -> gated scan, chained on the stream: the counts, the first candidate-bearing row and the listing
@@ -505,19 +512,7 @@ class RetrievalIndex:
 
     def _delete_list(self, indices):
         """what ``delete`` accepts -> sorted int64 [m] on the host, or ValueError"""
-        if torch.is_tensor(indices):
-            indices = indices.detach().cpu().numpy()
-        idx = np.atleast_1d(np.asarray(indices))
-        if idx.ndim != 1:
-            raise ValueError("delete takes a 1-D list of logical row indices, got shape %s" % (tuple(idx.shape),))
-        if idx.size == 0:
-            return np.zeros(0, dtype=np.int64)
-        if not np.issubdtype(idx.dtype, np.integer):
-            raise ValueError("delete takes integer row indices, got dtype %s" % idx.dtype)
-        if idx.min() < 0 or idx.max() >= self.n_db:
-            raise ValueError("delete: index outside [0, %d), the live rows of the window (a negative index does not count from the end)"
-                             % self.n_db)
-        idx = np.sort(idx.astype(np.int64))
+        idx = np.sort(_row_list(indices, self.n_db, "delete", rows="window", distinct=False))
         if (np.diff(idx) == 0).any():
             raise ValueError("delete: duplicate index %d" % idx[1:][np.diff(idx) == 0][0])
         if len(idx) >= self.n_db:
@@ -554,7 +549,7 @@ class RetrievalIndex:
 
     # ---- addressed by key -----------------------------------------------------------------------------------------------
     def _pool_form(self):
-        """where ops.pool_find / ops.pool_set_labels take the live rows from: the three forms of the scan"""
+        """where the ops wrappers (the scan, the assembly, pool_find, ...) take the live rows from: the three forms of the pool"""
         if self.capacity is None:
             return dict(n_rows=self.n_db)
         return dict(header=self.count, ring=self.window)
@@ -588,66 +583,61 @@ class RetrievalIndex:
         return int(found.numel())
 
 
-class _RequestGraph:
-    """retrieve -> assemble -> eval forward of one request size as one linear hipGraph (one stream, no parallel branches)"""
+class _ChainGraph:
+    """one chain of launches ending in the eval forward as one linear hipGraph (one stream, no parallel branches): the inputs are
+    cloned into static buffers and ``chain(*static)`` is captured under no_grad; what the chain reads besides — the pool's header, the
+    labels, the weights — is read at replay time"""
+
+    def __init__(self, chain, *inputs):
+        self.static = tuple(t.clone() for t in inputs)
+        self._stream = torch.cuda.Stream(device=inputs[0].device)
+        self.graph = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        with torch.no_grad(), torch.cuda.graph(self.graph, stream=self._stream, capture_error_mode="thread_local"):
+            self.y_pred = chain(*self.static)
+
+    def run(self, x):
+        if x.data_ptr() != self.static[0].data_ptr():
+            self.static[0].copy_(x, non_blocking=True)
+        self.graph.replay()
+        return self.y_pred.clone()
+
+
+class _RequestGraph(_ChainGraph):
+    """retrieve -> assemble -> eval forward of one request size; the ids are the static input"""
 
     def __init__(self, scorer, ids, same=None):
-        self.static_ids = ids.clone()
-        self._stream = torch.cuda.Stream(device=ids.device)
-        self.graph = torch.cuda.CUDAGraph()
-        torch.cuda.synchronize()
-        with torch.no_grad(), torch.cuda.graph(self.graph, stream=self._stream, capture_error_mode="thread_local"):
-            self.y_pred = scorer._score_eager(self.static_ids, same=same)
-
-    def run(self, ids):
-        if ids.data_ptr() != self.static_ids.data_ptr():
-            self.static_ids.copy_(ids, non_blocking=True)
-        self.graph.replay()
-        return self.y_pred.clone()
+        super().__init__(lambda static_ids: scorer._score_eager(static_ids, same=same), ids)
 
 
-class _RowsGraph:
-    """gather -> prepare -> horizon scan -> assemble -> eval forward of one number of pool rows as one linear hipGraph; the logical
-    indices are the static input"""
+class _RowsGraph(_ChainGraph):
+    """gather -> prepare -> horizon scan -> assemble -> eval forward of one number of pool rows; the logical indices are the static
+    input"""
 
     def __init__(self, scorer, indices, same=None):
-        self.static_idx = indices.clone()
-        self._stream = torch.cuda.Stream(device=indices.device)
-        self.graph = torch.cuda.CUDAGraph()
-        torch.cuda.synchronize()
-        with torch.no_grad(), torch.cuda.graph(self.graph, stream=self._stream, capture_error_mode="thread_local"):
-            self.y_pred = scorer._score_rows_eager(self.static_idx, same=same)
-
-    def run(self, indices):
-        if indices.data_ptr() != self.static_idx.data_ptr():
-            self.static_idx.copy_(indices, non_blocking=True)
-        self.graph.replay()
-        return self.y_pred.clone()
+        super().__init__(lambda static_idx: scorer._score_rows_eager(static_idx, same=same), indices)
 
 
-class _BucketGraph:
-    """the same chain for P rows (a power of two) that hold ANY mix of requests: ids and first_row are static inputs, refreshed before
-    each replay; linear on one stream like _RequestGraph"""
+class _BucketGraph(_ChainGraph):
+    """the request chain for P rows (a power of two) that hold ANY mix of requests: ids and first_row are static inputs, refreshed
+    before each replay"""
 
     def __init__(self, scorer, ids, first_row):
-        self.static_ids, self.static_first = ids.clone(), first_row.clone()
-        self._first_host = None        # the host array static_first was last uploaded from
-        self._stream = torch.cuda.Stream(device=ids.device)
-        self.graph = torch.cuda.CUDAGraph()
-        torch.cuda.synchronize()
-        with torch.no_grad(), torch.cuda.graph(self.graph, stream=self._stream, capture_error_mode="thread_local"):
-            self.y_pred = scorer._score_eager(self.static_ids, self.static_first)
+        super().__init__(scorer._score_eager, ids, first_row)
+        self._first_host = None        # the host array the static first_row was last uploaded from
 
     def run(self, ids, first_row):
         """first_row: a device tensor, or the host array it is built from — uploaded straight into the static buffer, and not at all
-        when it equals the last one (the same request sizes again: a batcher with fixed slots, one request of B rows)"""
-        self.static_ids.copy_(ids, non_blocking=True)
+        when it equals the last one (the same request sizes again: a batcher with fixed slots, one request of B rows).  Returns the
+        static y_pred, uncloned"""
+        static_ids, static_first = self.static
+        static_ids.copy_(ids, non_blocking=True)
         if torch.is_tensor(first_row):
             self._first_host = None
-            self.static_first.copy_(first_row, non_blocking=True)
+            static_first.copy_(first_row, non_blocking=True)
         elif self._first_host is None or not np.array_equal(first_row, self._first_host):
             self._first_host = first_row                                       # (kept: the upload reads it)
-            self.static_first.copy_(torch.from_numpy(first_row), non_blocking=True)
+            static_first.copy_(torch.from_numpy(first_row), non_blocking=True)
         self.graph.replay()
         return self.y_pred
 
@@ -708,15 +698,18 @@ class OnlineScorer:
                                    torch.zeros(B, dtype=torch.float32, device=self.device))
         return c
 
+    def _assemble_batch(self, ids, labels, neighbours):
+        """the rows (ids, labels) are the query table, ``neighbours`` their lists: logical positions in the row store, where -1 keeps its
+        numpy meaning, as offline — counted back from the pool's last LIVE row (a ring's newest)"""
+        form = self.index._pool_form()
+        form.pop("n_rows", None)                                               # the immutable row store holds the live rows and no others
+        rows, _zeros = self._constants(ids.shape[0])
+        return ops.batch_assemble(ids, labels, self.pool_ids, self.pool_labels, neighbours, rows, lib=self._lib, **form)
+
     def _assemble(self, ids, first_row=None, same=None):
-        rows, labels = self._constants(ids.shape[0])
+        _rows, labels = self._constants(ids.shape[0])
         _values, indices, _lens = self.index.retrieve(ids, _first_row=first_row, _exact=same)
-        # the request is the query table, the kernel's own index output the neighbour lists; -1 keeps its numpy meaning, as offline
-        if self.index.window:                                                  # ... logical positions in the ring, -1 its newest row
-            return ops.batch_assemble_ring(ids, labels, self.pool_ids, self.pool_labels, indices, rows, self.index.count, lib=self._lib)
-        if self.index.capacity is not None:                                    # ... counted back from the pool's last LIVE row
-            return ops.batch_assemble_dev(ids, labels, self.pool_ids, self.pool_labels, indices, rows, self.index.count, lib=self._lib)
-        return ops.batch_assemble(ids, labels, self.pool_ids, self.pool_labels, indices, rows, lib=self._lib)
+        return self._assemble_batch(ids, labels, indices)                      # the neighbour lists: the scan's own index output
 
     def _score_eager(self, ids, first_row=None, same=None):
         y_pred, _loss, _reg, _saved = self.model._run_forward(self._assemble(ids, first_row, same), save=False, with_reg=False)
@@ -758,6 +751,13 @@ class OnlineScorer:
             raise ValueError("labels must be a scalar or one label per index ([%d]), got shape %s" % (m, tuple(lab.shape)))
         return lab.contiguous()
 
+    def _index_list(self, indices, what):
+        """logical row indices -> int64 [m] on the device.  Host-side ones (a list, numpy, a host tensor) are validated (ValueError: a
+        non-integer dtype, an index outside [0, len(pool)), a duplicate, not 1-D); a DEVICE tensor is checked by shape and dtype and
+        passed through unread"""
+        idx = _device_list(indices, "%s takes a 1-D list of logical row indices" % what, "%s takes integer row indices" % what, self.device)
+        return idx if idx is not None else torch.from_numpy(_row_list(indices, len(self.index), what)).to(self.device)
+
     def set_labels(self, indices, labels):
         """The live rows at the logical positions ``indices`` get ``labels`` (a scalar for all, or [m], one per index) in place, in
         every form of the pool (``rat_pool_set_labels``).  A label is in no IDF table: nothing else moves, no captured request graph is
@@ -766,14 +766,7 @@ class OnlineScorer:
         index outside [0, len(pool)) or a duplicate.  A DEVICE tensor is passed through unread, without a synchronisation: entries < 0
         or >= len(pool) are skipped by the kernel (so the ``-1``-padded list of a find can be passed whole), and duplicates are the
         caller's business."""
-        if torch.is_tensor(indices) and indices.is_cuda:
-            if indices.ndim != 1:
-                raise ValueError("set_labels takes a 1-D list of logical row indices, got shape %s" % (tuple(indices.shape),))
-            if indices.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
-                raise ValueError("set_labels takes integer row indices, got dtype %s" % indices.dtype)
-            idx = indices.detach().to(self.device, torch.int64).contiguous()
-        else:
-            idx = torch.from_numpy(_row_list(indices, len(self.index), "set_labels")).to(self.device)
+        idx = self._index_list(indices, "set_labels")
         lab = self._labels(labels, idx.numel())
         if idx.numel():
             ops.pool_set_labels(self.pool_labels, idx, lab, lib=self._lib, **self.index._pool_form())
@@ -831,25 +824,13 @@ class OnlineScorer:
         same = self._same_key(same)
         ids = _as_device_ids(ids, self.device)
         with torch.no_grad():
-            if same is not None:
-                g = self._same_graph_for(ids, same)
-                return g.run(ids) if g is not None else self._score_eager(ids, same=same)
-            g = self._graph_for(ids)
-            return g.run(ids) if g is not None else self._score_eager(ids)
+            g = self._graph_for(ids, same)
+            return g.run(ids) if g is not None else self._score_eager(ids, same=same)
 
     # ---- the pool looks at itself ------------------------------------------------------------------------------------------
     def _row_indices(self, indices, what):
-        """logical row indices -> int64 [B] on the device.  Host-side ones are validated as ``set_labels`` validates them (ValueError:
-        a non-integer dtype, an index outside [0, len(pool)), a duplicate, not 1-D) and an empty list is refused; a DEVICE tensor is
-        checked by shape and dtype and passed through unread — the gather answers an index outside the live rows with a row of zeros"""
-        if torch.is_tensor(indices) and indices.is_cuda:
-            if indices.ndim != 1:
-                raise ValueError("%s takes a 1-D list of logical row indices, got shape %s" % (what, tuple(indices.shape)))
-            if indices.dtype not in _INT_DTYPES:
-                raise ValueError("%s takes integer row indices, got dtype %s" % (what, indices.dtype))
-            idx = indices.detach().to(self.device, torch.int64).contiguous()
-        else:
-            idx = torch.from_numpy(_row_list(indices, len(self.index), what)).to(self.device)
+        """``_index_list`` that refuses an empty list; the gather answers a device index outside the live rows with a row of zeros"""
+        idx = self._index_list(indices, what)
         if idx.numel() == 0:
             raise ValueError("%s: empty list of rows" % what)
         return idx
@@ -861,13 +842,7 @@ class OnlineScorer:
         ids, labels, before = ops.pool_gather_rows(self.pool_ids, self.pool_labels, idx, lib=self._lib, **form)
         _values, nbr, _lens = self.index.retrieve(ids, before=before, _exact=same)
         # a -1 padding is the newest row the query may see, not the pool's newest row (which the assembly would take for it)
-        nbr = torch.where(nbr < 0, (before - 1).clamp_(min=0).unsqueeze(1), nbr)
-        rows, _zeros = self._constants(idx.numel())
-        if self.index.window:
-            return ops.batch_assemble_ring(ids, labels, self.pool_ids, self.pool_labels, nbr, rows, self.index.count, lib=self._lib)
-        if self.index.capacity is not None:
-            return ops.batch_assemble_dev(ids, labels, self.pool_ids, self.pool_labels, nbr, rows, self.index.count, lib=self._lib)
-        return ops.batch_assemble(ids, labels, self.pool_ids, self.pool_labels, nbr, rows, lib=self._lib)
+        return self._assemble_batch(ids, labels, torch.where(nbr < 0, (before - 1).clamp_(min=0).unsqueeze(1), nbr))
 
     def _score_rows_eager(self, idx, same=None):
         y_pred, _loss, _reg, _saved = self.model._run_forward(self._assemble_rows(idx, same), save=False, with_reg=False)
@@ -893,11 +868,8 @@ class OnlineScorer:
         given_on_device = torch.is_tensor(indices) and indices.is_cuda
         idx = self._row_indices(indices, "score_rows")
         with torch.no_grad():
-            if same is not None:                                               # (``same``: as ``batch_rows``; graphs of its own)
-                g = self._same_rows_graph_for(idx, same) if given_on_device else None
-                return g.run(idx) if g is not None else self._score_rows_eager(idx, same)
-            g = self._rows_graph_for(idx) if given_on_device else None
-            return g.run(idx) if g is not None else self._score_rows_eager(idx)
+            g = self._rows_graph_for(idx, same) if given_on_device else None   # (``same``: as ``batch_rows``; graphs of its own)
+            return g.run(idx) if g is not None else self._score_rows_eager(idx, same)
 
     def _group_column(self, group):
         """``group``: None, or the index of one id column of the pool's rows -> that index, checked"""
@@ -939,27 +911,36 @@ class OnlineScorer:
         y_pred, labels, gids = self._rows_vectors(indices, same, group, "metrics_rows")
         return ops.eval_metrics(y_pred.contiguous(), labels, gids, lib=self._lib)
 
-    def _same_graph_for(self, ids, same):
-        """``_graph_for`` for ``score(ids, same=)``: a dictionary of its own, the key extended by the columns"""
+    def _graph_for(self, ids, same=None):
+        """the captured chain of ``score(ids)``, or None: launch eagerly.  ``same``: a dictionary of its own, the key extended by the
+        columns"""
         B = ids.shape[0]
         if not (self.graph and ids.is_cuda and B <= self.graph_max_batch):
             return None
-        key = (B, self.model._eval_graph_key((B, self.index.topK + 1, ids.shape[1])), same)
-        return self._captured(self._same_graphs, key, lambda: _RequestGraph(self, ids, same), "the online request with same=")
+        key = (B, self.model._eval_graph_key((B, self.index.topK + 1, ids.shape[1])))
+        if same is None:
+            return self._captured(self._graphs, key, lambda: _RequestGraph(self, ids), "the online request", self.graph_sizes)
+        return self._captured(self._same_graphs, key + (same,), lambda: _RequestGraph(self, ids, same), "the online request with same=",
+                              self.graph_sizes)
 
-    def _same_rows_graph_for(self, idx, same):
-        """``_rows_graph_for`` for ``score_rows(indices, same=)``"""
+    def _rows_graph_for(self, idx, same=None):
+        """``_graph_for`` for ``score_rows(indices)``"""
         B = idx.numel()
         if not (self.graph and idx.is_cuda and B <= self.graph_max_batch):
             return None
-        key = (B, self.model._eval_graph_key((B, self.index.topK + 1, self.index.row_len)), same)
-        return self._captured(self._same_rows_graphs, key, lambda: _RowsGraph(self, idx, same), "the pool-row scoring with same=")
+        key = (B, self.model._eval_graph_key((B, self.index.topK + 1, self.index.row_len)))
+        if same is None:
+            return self._captured(self._rows_graphs, key, lambda: _RowsGraph(self, idx), "the pool-row scoring", self.graph_sizes)
+        return self._captured(self._same_rows_graphs, key + (same,), lambda: _RowsGraph(self, idx, same),
+                              "the pool-row scoring with same=", self.graph_sizes)
 
-    def _captured(self, graphs, key, capture, what):
-        """the warm-up count and the capture of one entry of a ``same=`` dictionary (at most ``graph_sizes`` entries each)"""
+    def _captured(self, graphs, key, capture, what, limit=None):
+        """the entry ``key`` of one of the graph dictionaries (at most ``limit`` entries; None: any number): counts the eager calls up
+        to ``graph_warmup``, then captures once -> the graph, or None while the caller is to launch eagerly — during the warm-up, past
+        the limit, and for good after a capture that failed"""
         entry = graphs.get(key)
         if entry is None:
-            if len(graphs) >= self.graph_sizes:
+            if limit is not None and len(graphs) >= limit:
                 return None
             entry = graphs[key] = [0, None]
         if entry[1] is None:
@@ -969,31 +950,7 @@ class OnlineScorer:
             try:
                 entry[1] = capture()
             except Exception as exc:
-                import logging
                 logging.warning("hipGraph capture of %s failed (%s: %s); continuing with eager launches", what, type(exc).__name__, exc)
-                entry[1] = False
-        return entry[1] or None
-
-    def _rows_graph_for(self, idx):
-        B = idx.numel()
-        if not (self.graph and idx.is_cuda and B <= self.graph_max_batch):
-            return None
-        key = (B, self.model._eval_graph_key((B, self.index.topK + 1, self.index.row_len)))
-        entry = self._rows_graphs.get(key)
-        if entry is None:
-            if len(self._rows_graphs) >= self.graph_sizes:
-                return None
-            entry = self._rows_graphs[key] = [0, None]
-        if entry[1] is None:
-            entry[0] += 1
-            if entry[0] <= self.graph_warmup:
-                return None
-            try:
-                entry[1] = _RowsGraph(self, idx)
-            except Exception as exc:
-                import logging
-                logging.warning("hipGraph capture of the pool-row scoring failed (%s: %s); continuing with eager launches",
-                                type(exc).__name__, exc)
                 entry[1] = False
         return entry[1] or None
 
@@ -1061,41 +1018,5 @@ class OnlineScorer:
     def _bucket_graph_for(self, ids, first_row):
         P = ids.shape[0]
         key = (P, self.model._eval_graph_key((P, self.index.topK + 1, ids.shape[1])))
-        entry = self._bucket_graphs.get(key)
-        if entry is None:
-            entry = self._bucket_graphs[key] = [0, None]
-        if entry[1] is None:
-            entry[0] += 1
-            if entry[0] <= self.graph_warmup:
-                return None
-            try:
-                entry[1] = _BucketGraph(self, ids, self._on_device(first_row))
-            except Exception as exc:
-                import logging
-                logging.warning("hipGraph capture of the batched online requests failed (%s: %s); continuing with eager launches",
-                                type(exc).__name__, exc)
-                entry[1] = False
-        return entry[1] or None
-
-    def _graph_for(self, ids):
-        B = ids.shape[0]
-        if not (self.graph and ids.is_cuda and B <= self.graph_max_batch):
-            return None
-        key = (B, self.model._eval_graph_key((B, self.index.topK + 1, ids.shape[1])))
-        entry = self._graphs.get(key)
-        if entry is None:
-            if len(self._graphs) >= self.graph_sizes:
-                return None
-            entry = self._graphs[key] = [0, None]
-        if entry[1] is None:
-            entry[0] += 1
-            if entry[0] <= self.graph_warmup:
-                return None
-            try:
-                entry[1] = _RequestGraph(self, ids)
-            except Exception as exc:
-                import logging
-                logging.warning("hipGraph capture of the online request failed (%s: %s); continuing with eager launches",
-                                type(exc).__name__, exc)
-                entry[1] = False
-        return entry[1] or None
+        return self._captured(self._bucket_graphs, key, lambda: _BucketGraph(self, ids, self._on_device(first_row)),
+                              "the batched online requests")

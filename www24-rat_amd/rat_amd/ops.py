@@ -131,20 +131,31 @@ def split_weights_batch(job_array, njobs, like, lib=None):
 
 
 # ----------------------------------------------------------------------------- K0
-def batch_assemble(data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, lib=None):
-    """Device-side Dataset.__getitem__ + collate: -> (idx [B,1+K,L] int32, label_ids [B,1+K] int32, y_true [B] fp32)."""
+def batch_assemble(data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, header=None, ring=False, lib=None):
+    """Device-side Dataset.__getitem__ + collate: -> (idx [B,1+K,L] int32, label_ids [B,1+K] int32, y_true [B] fp32).
+    ``header`` (int64, device): the pool's row count is header[0], read on the device — a negative neighbour counts back from there
+    (rat_batch_assemble_dev).  With ``ring`` pool_ids [capacity, L] is a ring and header = [n, head]: neighbour indices are logical
+    positions, a negative one counts back from n (rat_batch_assemble_ring)."""
     lib = lib or get_lib()
     _chk(data_ids, torch.int32, "data_ids"), _chk(pool_ids, torch.int32, "pool_ids")
     _chk(data_labels, name="data_labels"), _chk(pool_labels, name="pool_labels")
-    _chk(retr_indices, torch.int64, "retr_indices"), _chk(rows, torch.int64, "rows")
+    _chk(retr_indices, torch.int64, "retr_indices"), _chk(rows, torch.int64, "rows"), _chk(header, torch.int64, "header")
     Q, L = data_ids.shape
     N, K, B = pool_ids.shape[0], retr_indices.shape[1], rows.numel()
     dev = data_ids.device
     idx = torch.empty((B, K + 1, L), dtype=torch.int32, device=dev)
     label_ids = torch.empty((B, K + 1), dtype=torch.int32, device=dev)
     y_true = torch.empty((B,), dtype=torch.float32, device=dev)
-    lib.call("rat_batch_assemble", _p(data_ids), _p(data_labels), _p(pool_ids), _p(pool_labels), _p(retr_indices), _p(rows),
-             _p(idx), _p(label_ids), _p(y_true), Q, N, B, K, L, _stream(data_ids))
+    head = (_p(data_ids), _p(data_labels), _p(pool_ids), _p(pool_labels), _p(retr_indices), _p(rows), _p(idx), _p(label_ids), _p(y_true), Q)
+    tail = (B, K, L, _stream(data_ids))
+    if ring:
+        assert header is not None and header.numel() >= 2 and pool_ids.shape[1] == L and pool_labels.numel() == N
+        lib.call("rat_batch_assemble_ring", *head, _p(header), N, *tail)
+    elif header is not None:
+        assert header.numel() >= 1
+        lib.call("rat_batch_assemble_dev", *head, _p(header), *tail)
+    else:
+        lib.call("rat_batch_assemble", *head, N, *tail)
     return idx, label_ids, y_true
 
 
@@ -953,23 +964,46 @@ def bm25_query_prepare(ids, cols, table_ids, table_idf, table_offsets, first_row
     return qry_ids, qry_idf
 
 
-def bm25_topk_split(db_t, qry_ids, qry_idf, topk, splits=0, lib=None):
-    """rat_bm25_topk over `splits` pool ranges (0: the library chooses) -> (values fp64 [Q, K], indices int64 [Q, K], lens int64 [Q]);
-    db_t int32 [F, N] field-major"""
-    lib = lib or get_lib()
+def _split_scan(lib, db_t, qry_ids, qry_idf, before, topk, splits):
+    """what every split scan checks and allocates -> (capacity, Q, F, the workspace (int64 words), the outputs (values fp64 [Q, K],
+    indices int64 [Q, K], lens int64 [Q]))"""
     _chk(db_t, torch.int32, "db_t"), _chk(qry_ids, torch.int32, "qry_ids"), _chk(qry_idf, torch.float64, "qry_idf")
-    F, N = db_t.shape
+    _chk(before, torch.int64, "before")
+    F, capacity = db_t.shape
     Q = qry_ids.shape[0]
     assert tuple(qry_ids.shape) == (Q, F) and tuple(qry_idf.shape) == (Q, F)
+    assert before is None or (before.ndim == 1 and before.numel() == Q)
     dev = db_t.device
     nbytes = lib.size("rat_bm25_topk_split_workspace", Q, int(topk), int(splits))
     ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
-    out_v = torch.empty((Q, topk), dtype=torch.float64, device=dev)
-    out_i = torch.empty((Q, topk), dtype=torch.int64, device=dev)
-    out_l = torch.empty((Q,), dtype=torch.int64, device=dev)
-    lib.call("rat_bm25_topk_split", _p(db_t), _p(qry_ids), _p(qry_idf), _p(out_v), _p(out_i), _p(out_l), _p(ws), ws.numel() * 8, N, Q, F,
-             int(topk), int(splits), _stream(db_t))
-    return out_v, out_i, out_l
+    out = (torch.empty((Q, topk), dtype=torch.float64, device=dev), torch.empty((Q, topk), dtype=torch.int64, device=dev),
+           torch.empty((Q,), dtype=torch.int64, device=dev))
+    return capacity, Q, F, ws, out
+
+
+def bm25_topk_split(db_t, qry_ids, qry_idf, topk, splits=0, before=None, header=None, ring=False, n_rows=None, lib=None):
+    """rat_bm25_topk over `splits` ranges (0: the library chooses, from the capacity) of the live rows of db_t int32 [F, capacity],
+    field-major -> (values fp64 [Q, K], indices int64 [Q, K], lens int64 [Q]).  The pool's form as in _pool_form: no header — all of
+    db_t (rat_bm25_topk_split; its row count is db_t's row stride as well, so ``n_rows`` can only repeat it); a header — its first
+    word is the row count, read on the device (rat_bm25_topk_split_dev); with ``ring`` the live rows start at slot header[1] and the
+    indices returned are logical positions (rat_bm25_topk_split_ring).  ``before`` (int64 [Q], device): query q sees the logical rows
+    i < before[q] only, clamped to [0, live row count] on the device (rat_bm25_topk_split_before, every form)."""
+    lib = lib or get_lib()
+    capacity, Q, F, ws, out = _split_scan(lib, db_t, qry_ids, qry_idf, before, topk, splits)
+    bufs, tail = [_p(t) for t in out] + [_p(ws), ws.numel() * 8], (Q, F, int(topk), int(splits), _stream(db_t))
+    if before is not None:
+        form, n_rows = _pool_form(header, ring, n_rows, capacity)
+        lib.call("rat_bm25_topk_split_before", _p(db_t), form, _p(header), n_rows, capacity, _p(qry_ids), _p(qry_idf), _p(before), *bufs,
+                 *tail)
+    elif ring or header is not None:
+        _chk(header, torch.int64, "header")
+        assert header is not None and header.numel() >= (2 if ring else 1)
+        lib.call("rat_bm25_topk_split_ring" if ring else "rat_bm25_topk_split_dev", _p(db_t), _p(header), _p(qry_ids), _p(qry_idf),
+                 *bufs, capacity, *tail)
+    else:
+        assert n_rows is None or int(n_rows) == capacity, "without a header the scan covers all of db_t: n_db is its row stride too"
+        lib.call("rat_bm25_topk_split", _p(db_t), _p(qry_ids), _p(qry_idf), *bufs, capacity, *tail)
+    return out
 
 
 # ----------------------------------------------------------------------------- K6c: a pool that grows in place (rat_amd/online.py)
@@ -986,42 +1020,6 @@ def pool_append(ids, labels, cols, db_t, count, pool_ids=None, pool_labels=None,
         assert tuple(pool_ids.shape) == (capacity, L) and pool_labels.numel() == capacity
     lib.call("rat_pool_append", _p(ids), _p(labels), _p(cols), _p(db_t), _p(pool_ids), _p(pool_labels), _p(count), M, capacity, L, F,
              _stream(db_t))
-
-
-def bm25_topk_split_dev(db_t, count, qry_ids, qry_idf, topk, splits=0, lib=None):
-    """bm25_topk_split over the first count[0] (int64, device) rows of db_t int32 [F, capacity]; splits = 0: chosen from the capacity"""
-    lib = lib or get_lib()
-    _chk(db_t, torch.int32, "db_t"), _chk(qry_ids, torch.int32, "qry_ids"), _chk(qry_idf, torch.float64, "qry_idf")
-    _chk(count, torch.int64, "count")
-    F, capacity = db_t.shape
-    Q = qry_ids.shape[0]
-    assert tuple(qry_ids.shape) == (Q, F) and tuple(qry_idf.shape) == (Q, F) and count.numel() >= 1
-    dev = db_t.device
-    nbytes = lib.size("rat_bm25_topk_split_workspace", Q, int(topk), int(splits))
-    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
-    out_v = torch.empty((Q, topk), dtype=torch.float64, device=dev)
-    out_i = torch.empty((Q, topk), dtype=torch.int64, device=dev)
-    out_l = torch.empty((Q,), dtype=torch.int64, device=dev)
-    lib.call("rat_bm25_topk_split_dev", _p(db_t), _p(count), _p(qry_ids), _p(qry_idf), _p(out_v), _p(out_i), _p(out_l), _p(ws),
-             ws.numel() * 8, capacity, Q, F, int(topk), int(splits), _stream(db_t))
-    return out_v, out_i, out_l
-
-
-def batch_assemble_dev(data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, count, lib=None):
-    """batch_assemble against a pool whose row count is count[0] (int64, device): a negative neighbour counts back from there"""
-    lib = lib or get_lib()
-    _chk(data_ids, torch.int32, "data_ids"), _chk(pool_ids, torch.int32, "pool_ids")
-    _chk(data_labels, name="data_labels"), _chk(pool_labels, name="pool_labels")
-    _chk(retr_indices, torch.int64, "retr_indices"), _chk(rows, torch.int64, "rows"), _chk(count, torch.int64, "count")
-    Q, L = data_ids.shape
-    K, B = retr_indices.shape[1], rows.numel()
-    dev = data_ids.device
-    idx = torch.empty((B, K + 1, L), dtype=torch.int32, device=dev)
-    label_ids = torch.empty((B, K + 1), dtype=torch.int32, device=dev)
-    y_true = torch.empty((B,), dtype=torch.float32, device=dev)
-    lib.call("rat_batch_assemble_dev", _p(data_ids), _p(data_labels), _p(pool_ids), _p(pool_labels), _p(retr_indices), _p(rows),
-             _p(idx), _p(label_ids), _p(y_true), Q, _p(count), B, K, L, _stream(data_ids))
-    return idx, label_ids, y_true
 
 
 # ----------------------------------------------------------------------------- a pool that slides: the same buffers as a ring
@@ -1125,50 +1123,11 @@ def pool_set_labels(pool_labels, indices, labels, header=None, ring=False, n_row
              0 if labels.numel() == 1 else 1, _stream(pool_labels))
 
 
-def bm25_topk_split_ring(db_t, header, qry_ids, qry_idf, topk, splits=0, lib=None):
-    """bm25_topk_split over the header[0] live rows of the ring db_t int32 [F, capacity], oldest (slot header[1]) first; the indices
-    returned are logical positions; splits = 0: chosen from the capacity"""
-    lib = lib or get_lib()
-    _chk(db_t, torch.int32, "db_t"), _chk(qry_ids, torch.int32, "qry_ids"), _chk(qry_idf, torch.float64, "qry_idf")
-    _chk(header, torch.int64, "header")
-    F, capacity = db_t.shape
-    Q = qry_ids.shape[0]
-    assert tuple(qry_ids.shape) == (Q, F) and tuple(qry_idf.shape) == (Q, F) and header.numel() >= 2
-    dev = db_t.device
-    nbytes = lib.size("rat_bm25_topk_split_workspace", Q, int(topk), int(splits))
-    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
-    out_v = torch.empty((Q, topk), dtype=torch.float64, device=dev)
-    out_i = torch.empty((Q, topk), dtype=torch.int64, device=dev)
-    out_l = torch.empty((Q,), dtype=torch.int64, device=dev)
-    lib.call("rat_bm25_topk_split_ring", _p(db_t), _p(header), _p(qry_ids), _p(qry_idf), _p(out_v), _p(out_i), _p(out_l), _p(ws),
-             ws.numel() * 8, capacity, Q, F, int(topk), int(splits), _stream(db_t))
-    return out_v, out_i, out_l
-
-
-def batch_assemble_ring(data_ids, data_labels, pool_ids, pool_labels, retr_indices, rows, header, lib=None):
-    """batch_assemble against a ring pool (pool_ids [capacity, L], header = [n, head] int64 on the device): neighbour indices are
-    logical positions, a negative one counts back from n"""
-    lib = lib or get_lib()
-    _chk(data_ids, torch.int32, "data_ids"), _chk(pool_ids, torch.int32, "pool_ids")
-    _chk(data_labels, name="data_labels"), _chk(pool_labels, name="pool_labels")
-    _chk(retr_indices, torch.int64, "retr_indices"), _chk(rows, torch.int64, "rows"), _chk(header, torch.int64, "header")
-    Q, L = data_ids.shape
-    K, B = retr_indices.shape[1], rows.numel()
-    assert header.numel() >= 2 and pool_ids.shape[1] == L and pool_labels.numel() == pool_ids.shape[0]
-    dev = data_ids.device
-    idx = torch.empty((B, K + 1, L), dtype=torch.int32, device=dev)
-    label_ids = torch.empty((B, K + 1), dtype=torch.int32, device=dev)
-    y_true = torch.empty((B,), dtype=torch.float32, device=dev)
-    lib.call("rat_batch_assemble_ring", _p(data_ids), _p(data_labels), _p(pool_ids), _p(pool_labels), _p(retr_indices), _p(rows),
-             _p(idx), _p(label_ids), _p(y_true), Q, _p(header), int(pool_ids.shape[0]), B, K, L, _stream(data_ids))
-    return idx, label_ids, y_true
-
-
 # ----------------------------------------------------------------------------- a pool that looks at itself (rat_amd/online.py)
 def pool_gather_rows(pool_ids, pool_labels, indices, header=None, ring=False, n_rows=None, lib=None):
     """-> (ids int32 [B, L], labels fp32 [B], before int64 [B]), on the device: the logical rows `indices` (int64 [B], device) of
     pool_ids int32 [capacity, L] / pool_labels fp32 [capacity]; an index < 0 or >= the live row count gives a row of zeros, label 0.
-    before = the indices clamped to [0, live row count] — every row's horizon for bm25_topk_split_before.  The pool's form as in
+    before = the indices clamped to [0, live row count] — every row's horizon for bm25_topk_split(before=).  The pool's form as in
     _pool_form."""
     lib = lib or get_lib()
     _chk(pool_ids, torch.int32, "pool_ids"), _chk(pool_labels, name="pool_labels"), _chk(indices, torch.int64, "indices")
@@ -1183,28 +1142,6 @@ def pool_gather_rows(pool_ids, pool_labels, indices, header=None, ring=False, n_
     lib.call("rat_pool_gather_rows", _p(pool_ids), _p(pool_labels), form, _p(header), n_rows, capacity, _p(indices), _p(out_ids),
              _p(out_labels), _p(out_before), B, L, _stream(pool_ids))
     return out_ids, out_labels, out_before
-
-
-def bm25_topk_split_before(db_t, qry_ids, qry_idf, before, topk, header=None, ring=False, n_rows=None, splits=0, lib=None):
-    """bm25_topk_split with a horizon per query: query q sees the logical rows i < before[q] (int64 [Q], device; clamped to
-    [0, live row count] on the device) of db_t int32 [F, capacity].  The pool's form as in _pool_form; splits = 0: chosen from the
-    capacity"""
-    lib = lib or get_lib()
-    _chk(db_t, torch.int32, "db_t"), _chk(qry_ids, torch.int32, "qry_ids"), _chk(qry_idf, torch.float64, "qry_idf")
-    _chk(before, torch.int64, "before")
-    F, capacity = db_t.shape
-    Q = qry_ids.shape[0]
-    assert tuple(qry_ids.shape) == (Q, F) and tuple(qry_idf.shape) == (Q, F) and before.ndim == 1 and before.numel() == Q
-    form, n_rows = _pool_form(header, ring, n_rows, capacity)
-    dev = db_t.device
-    nbytes = lib.size("rat_bm25_topk_split_workspace", Q, int(topk), int(splits))
-    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
-    out_v = torch.empty((Q, topk), dtype=torch.float64, device=dev)
-    out_i = torch.empty((Q, topk), dtype=torch.int64, device=dev)
-    out_l = torch.empty((Q,), dtype=torch.int64, device=dev)
-    lib.call("rat_bm25_topk_split_before", _p(db_t), form, _p(header), n_rows, capacity, _p(qry_ids), _p(qry_idf), _p(before), _p(out_v),
-             _p(out_i), _p(out_l), _p(ws), ws.numel() * 8, Q, F, int(topk), int(splits), _stream(db_t))
-    return out_v, out_i, out_l
 
 
 # ----------------------------------------------------------------------------- neighbours equal on given columns (rat_amd/online.py)
@@ -1243,26 +1180,17 @@ def bm25_exact_plan(counts, topk, lib=None):
 
 def bm25_topk_split_exact(db_t, qry_ids, qry_idf, exact_mask, listing, topk, before=None, header=None, ring=False, n_rows=None, splits=0,
                           lib=None):
-    """bm25_topk_split_before whose candidates are the rows equal to the query on the used columns in `exact_mask`: a candidate scores
-    (the weights of the other columns it matches) + 1, anything else 0; listing int32 [1] (device) != 0: each query's entries in
+    """bm25_topk_split(before=) whose candidates are the rows equal to the query on the used columns in `exact_mask`: a candidate
+    scores (the weights of the other columns it matches) + 1, anything else 0; listing int32 [1] (device) != 0: each query's entries in
     ascending index with value 1.0 instead.  before (int64 [Q], device) may be None.  The pool's form as in _pool_form."""
     lib = lib or get_lib()
-    _chk(db_t, torch.int32, "db_t"), _chk(qry_ids, torch.int32, "qry_ids"), _chk(qry_idf, torch.float64, "qry_idf")
-    _chk(before, torch.int64, "before"), _chk(listing, torch.int32, "listing")
-    F, capacity = db_t.shape
-    Q = qry_ids.shape[0]
-    assert tuple(qry_ids.shape) == (Q, F) and tuple(qry_idf.shape) == (Q, F) and listing.numel() >= 1
-    assert before is None or (before.ndim == 1 and before.numel() == Q)
+    _chk(listing, torch.int32, "listing")
+    assert listing.numel() >= 1
+    capacity, Q, F, ws, out = _split_scan(lib, db_t, qry_ids, qry_idf, before, topk, splits)
     form, n_rows = _pool_form(header, ring, n_rows, capacity)
-    dev = db_t.device
-    nbytes = lib.size("rat_bm25_topk_split_workspace", Q, int(topk), int(splits))
-    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
-    out_v = torch.empty((Q, topk), dtype=torch.float64, device=dev)
-    out_i = torch.empty((Q, topk), dtype=torch.int64, device=dev)
-    out_l = torch.empty((Q,), dtype=torch.int64, device=dev)
     lib.call("rat_bm25_topk_split_exact", _p(db_t), form, _p(header), n_rows, capacity, _p(qry_ids), _p(qry_idf), int(exact_mask),
-             _p(before), _p(listing), _p(out_v), _p(out_i), _p(out_l), _p(ws), ws.numel() * 8, Q, F, int(topk), int(splits), _stream(db_t))
-    return out_v, out_i, out_l
+             _p(before), _p(listing), *[_p(t) for t in out], _p(ws), ws.numel() * 8, Q, F, int(topk), int(splits), _stream(db_t))
+    return out
 
 
 # ----------------------------------------------------------------------------- evaluation metrics on the device (rat_amd/metrics.py)
