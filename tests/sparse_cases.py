@@ -2,7 +2,9 @@
 build on CPU (tests/test_sparse_grad.py) and the HIP build on the GPU (tests/test_gpu_sparse.py).
 
 Kernel level: plan + segmented reduction against CPU autograd's embedding_dense_backward on ids with heavy duplication, a bag
-field, padding ids and (reported elsewhere, ignored here) out-of-vocabulary ids; the merge of gathered per-rank lists.
+field, padding ids and (reported elsewhere, ignored here) out-of-vocabulary ids; the merge of gathered per-rank lists.  These are the
+loose end-to-end checks; the kernel-level suite of the plan and the reduce — every instantiation, bit for bit against a sequential
+float32 reference, past the grid caps — is tests/sparse_kernel_cases.py.
 Model level: `sorted` == `atomic` gradients (and bit-identical between two runs), `sparse` training == dense training wherever
 lazy Adam and dense Adam coincide (embedding_regularizer = 0: step 1 always; later steps when the same rows are touched)."""
 import numpy as np
@@ -58,7 +60,14 @@ def check_sorted_reduce(lib, dev, d, B=5, T=4, dup_vocab=3):
     close(dense, ref_dense, 1e-5, 1e-6 + 1e-7 * B * T, "dense sums")
     r = rows[:U].cpu().long()
     assert bool((r[1:] > r[:-1]).all()), "unique rows come out sorted"
-    assert not bool(((r == 6 + fields[0].vocab - 1 + 0) & False).any())
+    # the id 99 in column 0 lands on field 0's last row: that row's sum holds the entry's gradient (and is off by it without)
+    last = fields[0].vocab - 1
+    hit = idx[..., 0].clamp(0, last) == last
+    assert bool(hit[0, 1]) and int((r == last).sum()) == 1
+    want = dgrid[:, :, 1][hit].double().sum(0) + dflat[:, :d][hit[:, 0]].double().sum(0)
+    got_last = grads[:U].cpu()[r == last][0].double()
+    close(got_last, want, 1e-5, 1e-6 + 1e-7 * B * T, "the row the out-of-vocabulary id is clamped to")
+    assert float((got_last - (want - dgrid[0, 1, 1].double())).abs().max()) > 1e-3
     rebuilt = torch.zeros(total_rows, d)
     rebuilt[r] = grads[:U].cpu()
     assert torch.equal(rebuilt.reshape(-1), dense.cpu()), "row lists and the dense table hold the same bits"

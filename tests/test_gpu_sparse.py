@@ -1,5 +1,6 @@
 """Row-sparse / deterministic embedding-gradient path on the MI355X (-m gpu): rocPRIM's device radix sort + scan under the plan,
-the hand-written segmented reduction, the row optimizer — against CPU autograd and against the dense (atomic) path."""
+the hand-written segmented reduction, the row optimizer — against CPU autograd and against the dense (atomic) path.  The kernel level
+of the plan and the reduction (bit for bit, every instantiation, past the grid caps) is tests/test_gpu_sparse_kernels.py."""
 import numpy as np
 import pytest
 import torch

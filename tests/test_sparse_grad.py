@@ -1,5 +1,6 @@
 """Row-sparse / deterministic embedding-gradient path on CPU: the kernel sources through the host emulation (tests/emu), plus the
-2-rank gloo exchange of (row ids, gradient rows).  The GPU twin is tests/test_gpu_sparse.py."""
+2-rank gloo exchange of (row ids, gradient rows).  The GPU twin is tests/test_gpu_sparse.py; the kernel level of the plan and the
+segmented reduction (bit for bit, every instantiation) is tests/test_sparse_kernels.py."""
 import os
 import sys
 import tempfile
