@@ -836,6 +836,30 @@ size_t rat_eval_metrics_workspace(int64_t n, int grouped);
 int rat_eval_metrics(const float* y_pred, const float* y_true, const int32_t* group, int64_t n, double* out, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* The end of a request on the device (csrc/topn.hip; rat_amd/online.py: top_requests, top_candidates): a request is one user with a
+ * slate of candidates, and the caller wants the best n of them.  Both entry points take first_row (int64 [B], device) — for every
+ * batch row the row that opens its request, what rat_bm25_query_prepare_seg takes — and use f(b) = clamp(first_row[b], 0, B - 1):
+ * row h is a HEAD iff f(h) == h, its segment is h .. e - 1 with e the smallest j > h with f(j) != h, or B.  For valid first_row the
+ * segments are the requests; NO content of first_row (or of cols) leads to an address outside the buffers.  One launch each on
+ * `stream`, no atomics, nothing allocated, synchronised or read back.  -1 + rat_last_error() on a null pointer, B < 1 (or > 2^31 - 1),
+ * n, L or W out of range; nothing is launched then.
+ *
+ * rat_topn_seg: y fp32 [B] -> out_pos int32 [B][n], out_val fp32 [B][n], out_len int32 [B], 1 <= n <= RAT_MAX_TOPN.  At a head h:
+ *   out_len[h] = min(n, e - h); out_pos[h][i], i < out_len[h]: the positions INSIDE the segment (0-based) of its largest values, in
+ *   the order "a before b iff y[a] > y[b], or neither compares greater and a < b" with a NaN after every number — equal values (and
+ *   -0.0 / +0.0) by ascending position, NaNs among themselves by position: np.argsort(-y_seg, kind="stable")[:n] for any input;
+ *   out_val[h][i] = y[h + out_pos[h][i]], the same bits (y is only compared); the remaining entries are -1 and 0.0.  Every other row:
+ *   out_len 0 and a row of -1 / 0.0.  Every output element is written by every launch; the result is a function of the inputs alone.
+ *
+ * rat_candidates_expand: out[b][l] (int32 [B][L]) = cand[b][w] (int32 [B][W]) where l == cols[w] (int32 [W], device; distinct, in
+ *   [0, L) — an entry outside is skipped), otherwise ctx[f(b)][l] (int32 [B][L]: row h holds the context of the request that opens at
+ *   h; no other row is read).  1 <= L, W <= 8192.  16-byte accesses when L % 4 == 0 and ctx / out are 16-byte aligned. */
+#define RAT_MAX_TOPN 64
+int rat_topn_seg(const float* y, const int64_t* first_row, int64_t B, int n, int32_t* out_pos, float* out_val, int32_t* out_len,
+                 void* stream);
+int rat_candidates_expand(const int32_t* ctx, const int32_t* cand, const int32_t* cols, const int64_t* first_row, int64_t B, int L,
+                          int W, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,13 @@ split scan of the same pool form (immutable, capacity, window with the ring wrap
 measured as in --rows (i); the chain's result is compared bit for bit with the offline path (BM25_topk_retrieval_v4 with
 exact_match_col_indices) before anything is timed; (ii) replayed score(ids, same=) against replayed score(ids) at B in {1, 16, 256},
 host clock + synchronise, rounds of 200 alternating.
+--top — each request's best candidates instead (profiles/online/top_bench.txt), same geometry, the immutable pool, requests of one user
+row and C_r candidate items (the candidates differ in the item column), n = 10, on the grid R in {1, 16, 64} requests x C_r in {64, 256,
+1024} candidates within graph_max_batch: (i) device time per call of rat_topn_seg alone (a hipGraph of REPS calls, device events)
+and of the replayed top_candidates chain (its captured graph, device events), and the kernel's share; (ii) a replayed top_candidates call
+plus reading pos, y and lens back against the way without it — the rows expanded on the host, uploaded, a replayed score_requests, all
+predictions read back and a numpy stable top-n per request — host clock + synchronise, the sides alternating round by round, results
+compared before anything is timed; (iii) the bytes both ways move per call, derived from the shapes.
 There is no CPU fallback: without a GPU the tool exits with an error."""
 import argparse
 import os
@@ -793,6 +800,91 @@ def part_same(emit, quick):
     emit("   (%d score(same=) graphs, %d score() graphs)" % (len(scorer._same_graphs), len(scorer._graphs)))
 
 
+def part_top(emit, quick):
+    from rat_amd import ops
+    from rat_amd.online import OnlineScorer, _first_rows
+    name, model, rows, vocab, cfg, n_pool, _capacity = _movielens(quick)
+    dev = torch.device("cuda:0")
+    min_s = 0.05 if quick else MIN_TIMED_MS / 1e3
+    pool = rows(n_pool)
+    rs = np.random.RandomState(7)
+    scorer = OnlineScorer(model, pool, cfg, graph=True)
+    L, n, cols = len(vocab), 10, [1]                                        # the candidates of a request differ in the item column
+    W = len(cols)
+    grid = [(R, C) for R in ((1, 16) if quick else (1, 16, 64)) for C in (64, 256, 1024) if R * C <= scorer.graph_max_batch]
+    emit("== top: %s, %d-row pool, requests of one context row and C_r candidates (column %s), n = %d; grid within graph_max_batch = %d"
+         % (name, n_pool, cols, n, scorer.graph_max_batch))
+
+    def point(R, C_r):
+        C = R * C_r
+        contexts = np.stack([rs.randint(0, v, size=R) for v in vocab], axis=1).astype(np.int32)
+        cand = np.stack([rs.randint(0, vocab[c], size=C) for c in cols], axis=1).astype(np.int32)
+        off = (np.arange(R + 1) * C_r).astype(np.int64)
+        return C, contexts, cand, off
+
+    def host_way(contexts, cand, off):
+        """what a caller does without the ranked calls: expand on the host, upload, score, read everything back, sort per request"""
+        ids = np.repeat(contexts, np.diff(off), axis=0)
+        ids[:, cols] = cand
+        y = scorer.score_requests((ids, off))[0].cpu().numpy()
+        pos = np.full((len(off) - 1, n), -1, dtype=np.int32)
+        val = np.zeros((len(off) - 1, n), dtype=np.float32)
+        lens = np.zeros(len(off) - 1, dtype=np.int32)
+        for r, (a, b) in enumerate(zip(off[:-1], off[1:])):
+            order = np.argsort(-y[a:b], kind="stable")[:n]
+            pos[r, :len(order)], val[r, :len(order)], lens[r] = order, y[a:b][order], len(order)
+        return pos, val, lens
+
+    def ranked_way(contexts, cand, off):
+        pos, val, lens = scorer.top_candidates(contexts, cand, cols, off, n)
+        return pos.cpu().numpy(), val.cpu().numpy(), lens.cpu().numpy()
+
+    results = []
+    for R, C_r in grid:
+        C, contexts, cand, off = point(R, C_r)
+        for _ in range(scorer.graph_warmup + 2):
+            got = ranked_way(contexts, cand, off)
+            want = host_way(contexts, cand, off)
+        torch.cuda.synchronize()
+        P = 1 << (C - 1).bit_length()
+        chain = [e[1] for k, e in scorer._top_cand_graphs.items() if k[0] == P]
+        assert len(chain) == 1 and chain[0], "the ranked chain of %d rows was not captured" % P
+        same = all(np.array_equal(g.view(np.int32), w.view(np.int32)) for g, w in zip(got, want))
+        # (i) the kernel alone against the replayed chain, device events
+        y = torch.from_numpy(rs.rand(P).astype(np.float32)).to(dev)
+        first = _first_rows(off, None, C, dev, pad_to=P)
+        kernel, _ = _graph_of(lambda: ops.topn_seg(y, first, n), REPS)
+        t_kernel = time_alternating({"k": kernel}, REPS, 50.0 if quick else 200.0)["k"] * 1e3
+        t_chain = time_alternating({"c": chain[0].graph}, 1, 50.0 if quick else 200.0)["c"] * 1e3
+        # (ii) the two ways, host clock, alternating
+        per = {"ranked": [], "host": []}
+        while min(sum(v) for v in per.values()) / 1e6 < min_s or min(len(v) for v in per.values()) < 5:
+            for label, fn in (("ranked", ranked_way), ("host", host_way)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    fn(contexts, cand, off)
+                per[label].append((time.perf_counter() - t0) / 10 * 1e6)
+        results.append((R, C_r, C, P, t_kernel, t_chain, per, same))
+    emit("== top (i): device time per call [us]: rat_topn_seg alone (hipGraph of %d calls over P rows, device events) and the replayed "
+         "top_candidates chain (expand -> prepare -> scan -> assemble -> forward -> topn; its captured graph, device events)" % REPS)
+    for R, C_r, C, P, t_kernel, t_chain, per, same in results:
+        emit("R %3d x C_r %4d (P %4d) | rat_topn_seg %.1f | chain %.1f | share %.2f %%" % (R, C_r, P, t_kernel, t_chain, 100.0 * t_kernel / t_chain))
+    emit("== top (ii): one call [us], host clock: replayed top_candidates + pos, y and lens read back, against host expansion + upload + "
+         "replayed score_requests + all predictions read back + numpy stable top-n per request; rounds of 10 calls alternating; mean "
+         "(min .. max over the rounds)")
+    for R, C_r, C, P, t_kernel, t_chain, per, same in results:
+        a, b = (sum(per[k]) / len(per[k]) for k in ("ranked", "host"))
+        emit("R %3d x C_r %4d | ranked %s | host %s | host / ranked = %.2fx | results equal bit for bit: %s"
+             % (R, C_r, _stats(per["ranked"]), _stats(per["host"]), b / a, same))
+    emit("== top (iii): bytes per call, derived from the shapes (L = %d, W = %d, n = %d; both ways also upload first_row, 8 P bytes, when "
+         "the request sizes changed since the last call; the ranked way the R head rows besides, 8 R bytes)" % (L, W, n))
+    for R, C_r, C, P, _k, _c, _per, _same in results:
+        emit("R %3d x C_r %4d | H2D ranked %7d (R L + C W ids)  host %7d (C L ids) | D2H ranked %6d (R (8 n + 4))  host %6d (4 C)"
+             % (R, C_r, 4 * (R * L + C * W), 4 * C * L, R * (8 * n + 4), 4 * C))
+    emit("   (%d ranked-candidate graphs, %d bucket graphs)" % (len(scorer._top_cand_graphs), len(scorer._bucket_graphs)))
+
+
 class _SameSide:
     """score(ids, same=) behind the name _replay_round calls"""
 
@@ -818,6 +910,7 @@ def main():
     ap.add_argument("--requests", action="store_true", help="measure requests that share a launch (score_requests against R x score)")
     ap.add_argument("--rows", action="store_true", help="measure the pool that looks at itself (horizon scan against the plain scan; score_rows)")
     ap.add_argument("--same", action="store_true", help="measure neighbours restricted to equal columns (the chain against the plain scan; score(same=))")
+    ap.add_argument("--top", action="store_true", help="measure each request's top-n candidates (rat_topn_seg alone; top_candidates against the host way)")
     ap.add_argument("--trace", action="store_true", help="with --delete: only a few deletions per point, for a kernel trace")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -852,6 +945,9 @@ def main():
         return
     if args.same:
         part_same(emit, args.quick)
+        return
+    if args.top:
+        part_top(emit, args.quick)
         return
     part1(emit, args.quick)
     part2(emit, args.quick)

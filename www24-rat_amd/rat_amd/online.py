@@ -78,6 +78,18 @@ returns the candidates in ascending index with value 1.0), nothing read back in 
 ``graph=True`` the chains of ``score(ids, same=)`` and ``score_rows(indices, same=)`` are captured in dictionaries of their own, keyed
 by the columns as well; the ``same=None`` paths and their graphs are untouched.
 
+A request can end on the device.  A CTR request is one user with a slate of candidates, and the caller wants the best n of them:
+``top_requests(requests, n)`` runs ``score_requests``' chain unchanged, then ``rat_topn_seg`` — per request the positions and values
+of its n largest predictions in the order ``np.argsort(-y_request, kind="stable")[:n]`` (equal predictions in input order, a NaN
+last), values bit for bit, 1 <= n <= 64 — then one gather of the rows that open the requests, and returns device tensors (pos [R, n],
+y [R, n], lens [R]); nothing is read back in between.  ``top_candidates(contexts, candidates, cols, request_offsets, n)`` takes ONE
+encoded row per request and, for every candidate, only the columns ``cols`` in which the candidates differ: the contexts go to the
+rows that open their requests with one indexed copy, ``rat_candidates_expand`` builds the [C, L] ids on the device
+(``expand_candidates`` returns them), and the rest is ``top_requests``' chain — R L + C W ids go up instead of C L, R (8 n + 4) bytes
+come down instead of 4 C.  With ``graph=True`` the padding rule is ``score_requests``' and the chains are captured in two dictionaries
+of their own (``_top_graphs`` by bucket and n, ``_top_cand_graphs`` by the columns as well); the older calls and their graphs are
+untouched.  No ``same=`` / ``before=`` on these calls.
+
 Not served online (refused at construction): the config keys ``exact_match_cols`` / ``exact_match_col_indices`` (the restriction is
 per call, ``same=``; not built: ``same`` with ``request_offsets``, and all used columns exact), label-wise retrieval, topK > 32, more
 than 32 retrieval columns, data-parallel models.  Rows are deleted from a
@@ -94,6 +106,7 @@ from .data import DeviceBatch
 
 MAX_TOPK = 32
 MAX_COLS = 32
+MAX_TOPN = ops.MAX_TOPN          # candidates returned per request: a page of results
 
 
 def _as_device_ids(ids, device):
@@ -267,6 +280,33 @@ def _same_positions(same, col_list):
     if len(c) >= len(col_list):
         raise ValueError("same covers all %d used columns: at least one used column must remain to score" % len(col_list))
     return tuple(sorted(col_list.index(x) for x in c))
+
+
+def _top_n(n):
+    """what ``top_requests`` / ``top_candidates`` take as n -> int, or ValueError: an integer, 1 <= n <= MAX_TOPN"""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+        raise ValueError("n must be an integer (how many candidates to return per request), got %r" % (n,))
+    if not 1 <= int(n) <= MAX_TOPN:
+        raise ValueError("1 <= n <= %d (MAX_TOPN) is required, got n = %d" % (MAX_TOPN, int(n)))
+    return int(n)
+
+
+def _candidate_cols(cols, L):
+    """the columns of the encoded row that differ between the candidates of a request -> a tuple of ints in the caller's order, or
+    ValueError: a non-empty 1-D list of distinct integer column numbers inside [0, L)"""
+    if torch.is_tensor(cols):
+        cols = cols.detach().cpu().numpy()
+    c = np.asarray(cols)
+    if c.ndim != 1 or c.size == 0:
+        raise ValueError("cols takes a non-empty 1-D list of column numbers, got shape %s" % (tuple(c.shape),))
+    if not np.issubdtype(c.dtype, np.integer):
+        raise ValueError("cols takes integer column numbers, got dtype %s" % c.dtype)
+    c = tuple(int(x) for x in c)
+    if len(set(c)) != len(c):
+        raise ValueError("cols: repeated column in %s" % (c,))
+    if min(c) < 0 or max(c) >= L:
+        raise ValueError("cols: column %s outside [0, %d), the id columns of the encoded row" % ([x for x in c if not 0 <= x < L], L))
+    return c
 
 
 class _Exact(tuple):
@@ -642,6 +682,53 @@ class _BucketGraph(_ChainGraph):
         return self.y_pred
 
 
+class _HeadRows:
+    """the rows that open the requests, as the ranked calls gather them: a device tensor is passed through, a host array is uploaded
+    only when it differs from the last one (the same request sizes again)"""
+    _heads_host = _heads_dev = None
+
+    def heads(self, heads, device):
+        if torch.is_tensor(heads):
+            return heads
+        if self._heads_host is None or not np.array_equal(heads, self._heads_host):
+            self._heads_host, self._heads_dev = heads, torch.from_numpy(heads).to(device, non_blocking=True)
+        return self._heads_dev
+
+
+class _TopGraph(_BucketGraph, _HeadRows):
+    """the request chain for P rows followed by rat_topn_seg, for one n: ids and first_row are the static inputs; ``run`` returns the
+    static (pos [P, n], val [P, n], lens [P], y_pred [P]), uncloned"""
+
+    def __init__(self, scorer, n, ids, first_row):
+        _ChainGraph.__init__(self, lambda static_ids, static_first: scorer._top_eager(static_ids, static_first, n), ids, first_row)
+        self._first_host = None
+
+
+class _TopCandGraph(_ChainGraph, _HeadRows):
+    """rat_candidates_expand -> the request chain -> rat_topn_seg for P candidate rows, one n and one tuple of candidate columns: the
+    context slab, the candidates' columns and first_row are the static inputs.  The slab is refreshed at the head rows only (no other
+    row of it is read); first_row as in ``_BucketGraph.run``"""
+
+    def __init__(self, scorer, n, cols_dev, slab, cand, first_row):
+        super().__init__(lambda s, c, f: scorer._top_cand_eager(s, c, cols_dev, f, n), slab, cand, first_row)
+        self._cols = cols_dev          # (the captured launches read it)
+        self._first_host = None
+
+    def run(self, contexts, heads, cand, first_row):
+        """heads: the rows the contexts go to (the pad request's included), device tensor or host array"""
+        static_slab, static_cand, static_first = self.static
+        static_slab.index_copy_(0, self.heads(heads, static_slab.device), contexts)
+        static_cand.copy_(cand, non_blocking=True)
+        if torch.is_tensor(first_row):
+            self._first_host = None
+            static_first.copy_(first_row, non_blocking=True)
+        elif self._first_host is None or not np.array_equal(first_row, self._first_host):
+            self._first_host = first_row
+            static_first.copy_(torch.from_numpy(first_row), non_blocking=True)
+        self.graph.replay()
+        return self.y_pred
+
+
 class OnlineScorer:
     """``score(ids)``: fp32 [B] predictions of a trained model for fresh encoded rows ``ids`` [B, L], the neighbours retrieved from
     ``pool_array`` ([N, L + 1], label last) on the spot.  ``retrieval_configs`` is the dataset's block (``topK``, ``used_cols`` or
@@ -688,6 +775,9 @@ class OnlineScorer:
         self._rows_graphs = {}         # score_rows: key -> [eager calls seen, _RowsGraph | False | None]
         self._same_graphs = {}         # score(ids, same=): key + (the columns as ascending positions,) -> [eager requests seen, _RequestGraph | False | None]
         self._same_rows_graphs = {}    # score_rows(indices, same=): the same for _RowsGraph
+        self._top_graphs = {}          # top_requests: (bucket, n, ...) -> [eager calls seen, _TopGraph | False | None]
+        self._top_cand_graphs = {}     # top_candidates: (bucket, n, ..., the candidate columns) -> [eager calls seen, _TopCandGraph | False | None]
+        self._cols_dev = {}            # top_candidates: the candidate columns as a tuple -> the same as an int32 device tensor
         self._found = None             # relabel_where's index list (one entry per row the pool can hold), from its first call on
 
     # ------------------------------------------------------------------------------------------------------------------
@@ -1020,3 +1110,135 @@ class OnlineScorer:
         key = (P, self.model._eval_graph_key((P, self.index.topK + 1, ids.shape[1])))
         return self._captured(self._bucket_graphs, key, lambda: _BucketGraph(self, ids, self._on_device(first_row)),
                               "the batched online requests")
+
+    # ---- each request's best candidates ----------------------------------------------------------------------------------------
+    def _top_eager(self, ids, first_row, n):
+        """the request chain, then rat_topn_seg over its predictions -> (pos [B, n], val [B, n], lens [B], y_pred [B]); rows that open
+        no request hold padding"""
+        y_pred = self._score_eager(ids, first_row).contiguous()
+        return ops.topn_seg(y_pred, first_row, n, lib=self._lib) + (y_pred,)
+
+    def _top_cand_eager(self, slab, cand, cols_dev, first_row, n):
+        return self._top_eager(ops.candidates_expand(slab, cand, cols_dev, first_row, lib=self._lib), first_row, n)
+
+    def _heads(self, off_host, off_dev, B, pad, upload=True):
+        """the rows that open the requests, int64 [R] on the device (``pad``: and row B, which opens the pad request).  Device offsets
+        are used unread: clamped, so that the gather stays inside whatever they hold.  Host offsets with ``upload=False``: the host
+        array"""
+        if off_host is not None:
+            heads = np.ascontiguousarray(off_host[:-1] if not pad else np.concatenate([off_host[:-1], [B]]))
+            return torch.from_numpy(heads).to(self.device, non_blocking=True) if upload else heads
+        heads = off_dev[:-1].clamp(0, B - 1)
+        return torch.cat([heads, torch.full((1,), B, dtype=torch.int64, device=self.device)]) if pad else heads
+
+    @staticmethod
+    def _top_result(out, heads, B, scores):
+        pos, val, lens, y_pred = out
+        picked = (pos[heads], val[heads], lens[heads])                         # one gather each: new tensors, not the graph's buffers
+        return picked + (y_pred[:B].clone(),) if scores else picked
+
+    def top_requests(self, requests, n, scores=False):
+        """The best ``n`` rows of every request: ``requests`` as ``score_requests`` takes them (a LIST of [B_r, L] id arrays, or a
+        TUPLE (ids [B, L], request_offsets [R + 1], host or device)) -> device tensors (pos int32 [R, n], y fp32 [R, n], lens int32
+        [R]): ``pos[r, :lens[r]]`` are the positions INSIDE request r of its ``lens[r] = min(n, B_r)`` largest predictions, best
+        first — ``np.argsort(-y_r, kind="stable")[:n]``: equal predictions in input order — ``y[r]`` those predictions, the rest
+        ``-1`` / ``0.0``.  ``n`` larger than a request is no error.  ``scores=True``: additionally the full y_pred fp32 [B] that was
+        ranked.  The launches are ``score_requests``' chain, then ``rat_topn_seg``, then one gather of the rows that open the requests
+        — nothing is read back (device offsets are used unread).  1 <= n <= MAX_TOPN.  With ``graph=True`` the padding rule of
+        ``score_requests`` holds, and the chain of a (bucket, n) pair is captured after ``graph_warmup`` eager calls into
+        ``_top_graphs`` (at most ``graph_sizes`` pairs; others stay eager)."""
+        if self.model.training:
+            raise RuntimeError("OnlineScorer.top_requests needs the model in eval mode (model.eval())")
+        n = _top_n(n)
+        ids, off_host, off_dev = self._requests(requests)
+        B = ids.shape[0]
+        with torch.no_grad():
+            P = 1 << (B - 1).bit_length()
+            if not (self.graph and ids.is_cuda and P <= self.graph_max_batch):
+                out = self._top_eager(ids, _first_rows(off_host, off_dev, B, self.device), n)
+                return self._top_result(out, self._heads(off_host, off_dev, B, False), B, scores)
+            first_row = _first_rows(off_host, off_dev, B, self.device, pad_to=P, upload=False)
+            if P > B:                                                          # the pad rows: valid ids, a request of their own
+                ids = torch.cat([ids, ids[:1].expand(P - B, -1)])
+            key = (P, n, self.model._eval_graph_key((P, self.index.topK + 1, ids.shape[1])))
+            g = self._captured(self._top_graphs, key, lambda: _TopGraph(self, n, ids, self._on_device(first_row)),
+                               "the ranked online requests", self.graph_sizes)
+            if g is not None:
+                return self._top_result(g.run(ids, first_row), g.heads(self._heads(off_host, off_dev, B, False, upload=False), self.device), B, scores)
+            return self._top_result(self._top_eager(ids, self._on_device(first_row), n), self._heads(off_host, off_dev, B, False), B, scores)
+
+    def _candidates(self, contexts, candidates, cols, request_offsets):
+        """what ``top_candidates`` takes -> (contexts int32 [R, L], candidates int32 [C, W], the columns as a tuple and as an int32
+        device tensor, host offsets | None, device offsets | None), or ValueError with nothing launched"""
+        L = self.index.row_len
+        cols = _candidate_cols(cols, L)
+        shapes = []                                                            # everything that can be refused, before the first upload
+        for t, what in ((contexts, "contexts must be [R, L] encoded rows"), (candidates, "candidates must be [C, W] ids")):
+            shapes.append(tuple(t.shape) if hasattr(t, "shape") else np.shape(t))
+            if len(shapes[-1]) != 2:
+                raise ValueError("%s, got shape %s" % (what, shapes[-1]))
+        (R_given, L_given), (C, W) = shapes
+        if L_given != L:
+            raise ValueError("contexts have %d columns, the pool's rows have %d" % (L_given, L))
+        if W != len(cols):
+            raise ValueError("candidates have %d columns for the %d columns in cols" % (W, len(cols)))
+        if C == 0:
+            raise ValueError("empty request")
+        off_host, off_dev = _request_offsets(request_offsets, C)
+        R = (len(off_host) if off_host is not None else off_dev.numel()) - 1
+        if R_given != R:
+            raise ValueError("contexts hold %d rows for %d requests (one encoded row per request)" % (R_given, R))
+        contexts, candidates = _as_device_ids(contexts, self.device), _as_device_ids(candidates, self.device)
+        cols_dev = self._cols_dev.get(cols)
+        if cols_dev is None:                                                   # one upload per tuple of columns
+            cols_dev = self._cols_dev[cols] = torch.tensor(cols, dtype=torch.int32).to(self.device)
+        return contexts, candidates, cols, cols_dev, off_host, off_dev
+
+    def _slab(self, contexts, heads, rows):
+        """[rows, L] with the contexts at the rows that open their requests: one indexed copy; no other row is ever read"""
+        return torch.empty((rows, contexts.shape[1]), dtype=torch.int32, device=self.device).index_copy_(0, heads, contexts)
+
+    def expand_candidates(self, contexts, candidates, cols, request_offsets):
+        """-> ids int32 [C, L] on the device: the full encoded row of every candidate — the columns ``cols`` from ``candidates``
+        [C, W], every other column from the context row of the candidate's request (``contexts`` [R, L]; request r owns the candidates
+        ``request_offsets[r] .. request_offsets[r + 1] - 1``).  What ``top_candidates`` scores; built by ``rat_candidates_expand``."""
+        contexts, candidates, _cols, cols_dev, off_host, off_dev = self._candidates(contexts, candidates, cols, request_offsets)
+        C = candidates.shape[0]
+        slab = self._slab(contexts, self._heads(off_host, off_dev, C, False), C)
+        return ops.candidates_expand(slab, candidates, cols_dev, _first_rows(off_host, off_dev, C, self.device), lib=self._lib)
+
+    def top_candidates(self, contexts, candidates, cols, request_offsets, n, scores=False):
+        """``top_requests`` for requests given as ONE context row each plus the columns in which their candidates differ:
+        ``contexts`` [R, L] encoded rows (their ``cols`` entries are ignored), ``candidates`` [C, W] the ids of the columns ``cols``
+        (W distinct column numbers of the encoded row) of all C candidates, ``request_offsets`` [R + 1] over the candidates (host:
+        validated; device: used unread).  The caller uploads R L + C W ids instead of C L: the rows are built on the device
+        (``rat_candidates_expand``, after one indexed copy of the contexts to the rows that open their requests), and the rest is
+        ``top_requests``' chain.  Returns what ``top_requests`` returns, positions counting the candidates of a request from 0.
+        With ``graph=True`` the chain of a (bucket, n, cols) triple is captured into ``_top_cand_graphs``."""
+        if self.model.training:
+            raise RuntimeError("OnlineScorer.top_candidates needs the model in eval mode (model.eval())")
+        n = _top_n(n)
+        contexts, cand, cols, cols_dev, off_host, off_dev = self._candidates(contexts, candidates, cols, request_offsets)
+        C = cand.shape[0]
+        with torch.no_grad():
+            P = 1 << (C - 1).bit_length()
+            if not (self.graph and cand.is_cuda and P <= self.graph_max_batch):
+                slab = self._slab(contexts, self._heads(off_host, off_dev, C, False), C)
+                out = self._top_cand_eager(slab, cand, cols_dev, _first_rows(off_host, off_dev, C, self.device), n)
+                return self._top_result(out, self._heads(off_host, off_dev, C, False), C, scores)
+            first_row = _first_rows(off_host, off_dev, C, self.device, pad_to=P, upload=False)
+            heads = self._heads(off_host, off_dev, C, P > C, upload=False)
+            if P > C:                                                          # the pad request: the first request's context, copies of its first candidate
+                contexts = torch.cat([contexts, contexts[:1]])
+                cand = torch.cat([cand, cand[:1].expand(P - C, -1)])
+            key = (P, n, self.model._eval_graph_key((P, self.index.topK + 1, contexts.shape[1])), cols)
+            g = self._captured(self._top_cand_graphs, key,
+                               lambda: _TopCandGraph(self, n, cols_dev, self._slab(contexts, self._on_device(heads), P), cand,
+                                                     self._on_device(first_row)),
+                               "the ranked candidate requests", self.graph_sizes)
+            if g is not None:
+                out, heads = g.run(contexts, heads, cand, first_row), g.heads(heads, self.device)
+            else:
+                heads = self._on_device(heads)
+                out = self._top_cand_eager(self._slab(contexts, heads, P), cand, cols_dev, self._on_device(first_row), n)
+            return self._top_result(out, heads[:-1] if P > C else heads, C, scores)

@@ -1214,3 +1214,61 @@ def eval_metrics(y_pred, y_true, group=None, lib=None):
     out = torch.empty(8, dtype=torch.float64, device=dev)
     lib.call("rat_eval_metrics", _p(y_pred), _p(y_true), _p(group), n, _p(out), _p(ws), nbytes, _stream(y_pred))
     return out
+
+
+# ----------------------------------------------------------------------------- the end of a request (rat_amd/online.py)
+MAX_TOPN = 64                                          # RAT_MAX_TOPN
+
+
+def _first_row_arg(first_row, B, dev, what):
+    """first_row int64 [B] on `dev`, checked by shape, dtype and device; its contents are the kernels' business (they clamp)"""
+    _chk(first_row, torch.int64, "first_row")
+    if tuple(first_row.shape) != (B,):
+        raise ValueError("%s: first_row must be [%d] (one entry per row), got shape %s" % (what, B, tuple(first_row.shape)))
+    if first_row.device != dev:
+        raise ValueError("%s: the tensors sit on different devices" % what)
+
+
+def topn_seg(y, first_row, n, lib=None):
+    """-> (pos int32 [B, n], val fp32 [B, n], lens int32 [B]) on the inputs' device, nothing read back: at every row h that opens a
+    request — first_row[h] == h; first_row int64 [B]: for every row the row that opens its request — the positions inside the request
+    and the values of its min(n, request size) largest entries of y fp32 [B], in the order np.argsort(-y_request, kind="stable")[:n],
+    padded with -1 / 0.0; lens[h] their number.  Every other row: -1 / 0.0 / 0.  1 <= n <= MAX_TOPN (include/rat_hip.h: rat_topn_seg)."""
+    lib = lib or get_lib()
+    _chk(y, name="y")
+    if y.ndim != 1 or y.numel() < 1:
+        raise ValueError("topn_seg takes a non-empty 1-D vector y, got shape %s" % (tuple(y.shape),))
+    B, dev = y.numel(), y.device
+    _first_row_arg(first_row, B, dev, "topn_seg")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= MAX_TOPN:
+        raise ValueError("topn_seg takes an integer 1 <= n <= %d, got %r" % (MAX_TOPN, n))
+    n = int(n)
+    pos = torch.empty((B, n), dtype=torch.int32, device=dev)
+    val = torch.empty((B, n), dtype=torch.float32, device=dev)
+    lens = torch.empty((B,), dtype=torch.int32, device=dev)
+    lib.call("rat_topn_seg", _p(y), _p(first_row), B, n, _p(pos), _p(val), _p(lens), _stream(y))
+    return pos, val, lens
+
+
+def candidates_expand(ctx, cand, cols, first_row, lib=None):
+    """-> ids int32 [B, L] on the inputs' device: ids[b, cols[w]] = cand[b, w] (cand int32 [B, W], cols int32 [W] on the device,
+    distinct and in [0, L)), every other column from ctx[first_row[b]] (ctx int32 [B, L]: the row that opens a request holds the
+    request's context, no other row is read; first_row int64 [B]) — the full rows of a request's candidates from one context row
+    (include/rat_hip.h: rat_candidates_expand)."""
+    lib = lib or get_lib()
+    _chk(ctx, torch.int32, "ctx"), _chk(cand, torch.int32, "cand"), _chk(cols, torch.int32, "cols")
+    if ctx.ndim != 2 or cand.ndim != 2 or cols.ndim != 1 or ctx.shape[0] < 1 or ctx.shape[1] < 1 or cols.numel() < 1:
+        raise ValueError("candidates_expand takes ctx [B, L], cand [B, W] and cols [W], got shapes %s, %s, %s"
+                         % (tuple(ctx.shape), tuple(cand.shape), tuple(cols.shape)))
+    B, L = ctx.shape
+    W = cols.numel()
+    if tuple(cand.shape) != (B, W):
+        raise ValueError("candidates_expand: cand must be [%d, %d] (one row per row of ctx, one column per entry of cols), got shape %s"
+                         % (B, W, tuple(cand.shape)))
+    dev = ctx.device
+    if cand.device != dev or cols.device != dev:
+        raise ValueError("candidates_expand: the tensors sit on different devices")
+    _first_row_arg(first_row, B, dev, "candidates_expand")
+    out = torch.empty((B, L), dtype=torch.int32, device=dev)
+    lib.call("rat_candidates_expand", _p(ctx), _p(cand), _p(cols), _p(first_row), B, L, W, _p(out), _stream(ctx))
+    return out
