@@ -366,6 +366,28 @@ struct HeadVec {
             for (int c = 0; c < N; ++c) v[c] = (TDH > 0 || c < dh) ? p[c] : 0.f;
         }
     }
+    // load() of a row that lives in LDS, as N / 2 separate ds_read_b64.  hipcc pairs the adjacent 8-byte loads of load() into
+    // ds_read2_b64, which the LDS array serves at half the bytes per clock of the plain form (8 cycles for 16 bytes per lane
+    // against 2 x 2); a volatile access through an LDS-address-space pointer is left unpaired and its waits stay compiler-tracked.
+    // Same values into the same registers: what is computed from them is bit-identical.
+    template <bool UNPAIRED = true>
+    __device__ __forceinline__ void load_lds(const float* p, int dh) {
+#if !defined(RAT_EMU)
+        if (UNPAIRED && TDH > 0 && TDH % 2 == 0) {
+            typedef float f32x2 __attribute__((ext_vector_type(2)));
+            typedef const volatile __attribute__((address_space(3))) f32x2* lds_f32x2_ptr;
+            const lds_f32x2_ptr q = (lds_f32x2_ptr)p;
+#pragma unroll
+            for (int c = 0; c < N; c += 2) {
+                const f32x2 t = q[c >> 1];
+                v[c] = t.x;
+                v[c + 1] = t.y;
+            }
+            return;
+        }
+#endif
+        load(p, dh);
+    }
     __device__ __forceinline__ void store(float* p, int dh, float scale) const {
         if (TDH > 0 && TDH % 2 == 0) {
 #pragma unroll

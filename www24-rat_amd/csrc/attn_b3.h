@@ -11,6 +11,11 @@
 //     16-byte L2 loads of pre-split weight fragments;
 //   * Q|K|V, dO and O stay fp32 tiles for the VALU attention core, which is unchanged (same instruction sequence => the softmax
 //     statistics, the saved O / log-sum-exp and the pass structure are those of the exact-fp32 kernels).
+//   * The core loops of the 8 heads x 10 instantiations (no DPAD, no GRP) read their rows — K / V in the forward and in pass 1 of the
+//     backward, dO / Q in pass 2 — through HeadVec::load_lds: five unpaired ds_read_b64 per row instead of the ds_read2_b64 pairs hipcc
+//     makes of plain loads (half the LDS-array cycles for the same bytes, MI355X LDS table), and pass 2 — where it needs both, i.e.
+//     without the hand-over of the probabilities — fetches a query's {lse, delta} in one 8-byte read of an interleaved array.  Same
+//     values into the same arithmetic: every output is bit-identical.  Measurements: profiles/attn_core_reads/.
 constexpr int B3_D = 64, B3_I = 80, B3_Q3 = 240, B3_H = 8, B3_DH = 10;
 constexpr int B3_LDQ = B3_Q3 + 4;                      // fp32 Q|K|V tile row (floats)
 constexpr int B3_XP = 64 * 128;                         // one plane of a [64][64] tile (128-byte rows, swizzled)
@@ -320,6 +325,7 @@ __device__ __forceinline__ void b3_fwd_core_mfma(float* qkv, float* lse_s, int L
 template <bool EX, bool QSUB = false, bool DPAD = false, bool GRP = false, int MCF = 0, int NH = B3_H>
 __global__ void __launch_bounds__(ATT_THREADS) attn_fwd3_kernel(AttnArgs a, Attn3W W) {
     constexpr int NDH = B3_I / NH;
+    constexpr bool RD = NH == B3_H && !GRP && !DPAD;      // the core's K / V rows as unpaired 8-byte LDS reads (HeadVec::load_lds)
     static_assert(NH == B3_H || (NH == 4 && MCF == 0 && !GRP && !DPAD), "the matrix cores, the group loop and DPAD are written for 8 heads x 10");
     static_assert(!GRP || (EX && !QSUB && !DPAD), "the group loop is written for the general (EX) form at embedding_dim 64");
     static_assert(MCF == 0 || !QSUB, "the matrix core computes every query");
@@ -420,8 +426,8 @@ __global__ void __launch_bounds__(ATT_THREADS) attn_fwd3_kernel(AttnArgs a, Attn
 #pragma unroll
                 for (int u = 0; u < CORE_UNROLL; ++u) {
                     const float* kp = kbase + (size_t)(j + u) * B3_LDQ;
-                    kk[u].load(kp, NDH);
-                    vv[u].load(kp + B3_I, NDH);
+                    kk[u].template load_lds<RD>(kp, NDH);
+                    vv[u].template load_lds<RD>(kp + B3_I, NDH);
                 }
                 float sc[CORE_UNROLL];
 #pragma unroll
@@ -438,13 +444,13 @@ __global__ void __launch_bounds__(ATT_THREADS) attn_fwd3_kernel(AttnArgs a, Attn
             }
             for (; j < L; ++j) {
                 const float* kp = kbase + (size_t)j * B3_LDQ;
-                kv.load(kp, NDH);
+                kv.template load_lds<RD>(kp, NDH);
                 const float sv = q.dot(kv) * sl2;
                 const float mn = fmaxf(m, sv);
                 const float corr = rat_exp2(m - mn);
                 const float p = rat_exp2(sv - mn);
                 l = l * corr + p;
-                kv.load(kp + B3_I, NDH);
+                kv.template load_lds<RD>(kp + B3_I, NDH);
                 o.scale_axpy(corr, p, kv);
                 m = mn;
             }
@@ -701,15 +707,19 @@ __global__ void __launch_bounds__(ATT_THREADS, 4) attn_fwd3_2wg_kernel(AttnArgs 
             int j = 0;
             for (; j + CORE_UNROLL <= L; j += CORE_UNROLL) {
                 HV kk[CORE_UNROLL], vv[CORE_UNROLL];
+                // (unpaired reads go out in program order: the K rows first.  <false> keeps the residual's x piece in 8 registers across the
+                //  core: with all six rows in flight at once it needs 130 VGPRs and spills, so there the trip's last V row is requested
+                //  behind the scores, into the registers the K rows leave)
+                constexpr int NV0 = EX ? CORE_UNROLL : CORE_UNROLL - 1;
 #pragma unroll
-                for (int u = 0; u < CORE_UNROLL; ++u) {
-                    const float* kp = kbase + (size_t)(j + u) * B3_LDK2;
-                    kk[u].load(kp, B3_DH);
-                    vv[u].load(kp + B3_I, B3_DH);
-                }
+                for (int u = 0; u < CORE_UNROLL; ++u) kk[u].load_lds(kbase + (size_t)(j + u) * B3_LDK2, B3_DH);
+#pragma unroll
+                for (int u = 0; u < NV0; ++u) vv[u].load_lds(kbase + (size_t)(j + u) * B3_LDK2 + B3_I, B3_DH);
                 float sc[CORE_UNROLL];
 #pragma unroll
                 for (int u = 0; u < CORE_UNROLL; ++u) sc[u] = q.dot(kk[u]) * sl2;
+#pragma unroll
+                for (int u = NV0; u < CORE_UNROLL; ++u) vv[u].load_lds(kbase + (size_t)(j + u) * B3_LDK2 + B3_I, B3_DH);
 #pragma unroll
                 for (int u = 0; u < CORE_UNROLL; ++u) {
                     const float mn = fmaxf(m, sc[u]);
@@ -722,13 +732,13 @@ __global__ void __launch_bounds__(ATT_THREADS, 4) attn_fwd3_2wg_kernel(AttnArgs 
             }
             for (; j < L; ++j) {
                 const float* kp = kbase + (size_t)j * B3_LDK2;
-                kk1.load(kp, B3_DH);
+                kk1.load_lds(kp, B3_DH);
                 const float sv = q.dot(kk1) * sl2;
                 const float mn = fmaxf(m, sv);
                 const float corr = rat_exp2(m - mn);
                 const float p = rat_exp2(sv - mn);
                 l = l * corr + p;
-                kk1.load(kp + B3_I, B3_DH);
+                kk1.load_lds(kp + B3_I, B3_DH);
                 o.scale_axpy(corr, p, kk1);
                 m = mn;
             }
@@ -1154,6 +1164,12 @@ static_assert((size_t)ATT_WAVES * (16 * 33 + 16) * 4 <= (size_t)3 * B3_XP, "the 
 template <bool EX, bool QSUB = false, bool DPAD = false, bool PH = false, int MC = 0, int NH = B3_H>
 __global__ void __launch_bounds__(ATT_THREADS) attn_bwd3_kernel(AttnArgs a, Attn3W W) {
     constexpr int NDH = B3_I / NH;
+    constexpr bool RD = NH == B3_H && !DPAD;              // the passes' K / V / dO / Q rows as unpaired 8-byte LDS reads (HeadVec::load_lds)
+    // lse / delta of (row, head) e = row NH + head: two arrays [64][NH], or — where pass 2 needs both (the VALU passes without the hand-over
+    // of the probabilities) — interleaved as [64][8]{lse, delta}, so that pass 2 fetches a query's pair in one 8-byte read
+    constexpr bool LSD2 = RD && MC == 0 && !PH;
+    auto lse_at = [](int e) { return LSD2 ? 2 * e : e; };
+    auto dlt_at = [](int e) { return LSD2 ? 2 * e + 1 : ATT_ROWS * NH + e; };
     static_assert(NH == B3_H || (NH == 4 && MC == 0 && !DPAD), "the matrix core and DPAD are written for 8 heads x 10");
     static_assert(MC == 0 || (!QSUB && !PH), "the matrix core computes every query and hands nothing over");   // MC = 16-row tiles per sequence (1 / 2)
     RAT_DYN_SMEM(smem);
@@ -1166,9 +1182,8 @@ __global__ void __launch_bounds__(ATT_THREADS) attn_bwd3_kernel(AttnArgs a, Attn
     float* dob = reinterpret_cast<float*>(smem + B3_OFF_DOB);                // [64][84] dO
     float* mu = reinterpret_cast<float*>(smem + B3_OFF_MISC);
     float* rs = mu + ATT_ROWS;
-    float* lses = rs + ATT_ROWS;                                             // [64][8]
-    float* dlt = lses + ATT_ROWS * NH;                                     // [64][8]
-    int64_t* const rowtok0 = reinterpret_cast<int64_t*>(dlt + ATT_ROWS * NH);
+    float* lsd = rs + ATT_ROWS;                                              // [64][NH] lse | [64][NH] delta, or interleaved (LSD2 above)
+    int64_t* const rowtok0 = reinterpret_cast<int64_t*>(lsd + 2 * ATT_ROWS * NH);
     const int L = a.L;
     const int r_own = threadIdx.x >> 3, sub = threadIdx.x & 7;               // this thread's (row slot, 8-column piece)
     const int dreal = DPAD ? a.d : B3_D;                                     // DPAD: embedding_dim 40 / 48 / 56 inside the 64-wide tiles
@@ -1245,7 +1260,7 @@ __global__ void __launch_bounds__(ATT_THREADS) attn_bwd3_kernel(AttnArgs a, Attn
             rat_split8(d0, d1, h, m, l);
             dyp.store(r_own, sub, h, m, l);
             fo.stash(ob, B3_LDT);
-            if (sub < NH) lses[r_own * NH + sub] = lsen;                     // (NH = 8: 512 threads = 64 rows x 8 heads)
+            if (sub < NH) lsd[lse_at(r_own * NH + sub)] = lsen;                     // (NH = 8: 512 threads = 64 rows x 8 heads)
         }
         if (chunk + gridDim.x < a.nchunks) {
             int nsq1, rows1;
@@ -1309,8 +1324,8 @@ __global__ void __launch_bounds__(ATT_THREADS) attn_bwd3_kernel(AttnArgs a, Attn
         const int nq = QSUB ? a.nq : L;
         const int ntasks = nsq * NH * L, nqtasks = QSUB ? nsq * NH * nq : ntasks;
         const float sl2 = a.scale * RAT_LOG2E;
-        if (MC >= 10) b3_bwd_core_mfma_kt<(MC >= 10 ? MC % 10 : 1)>(qkv, ob, dob, lses, dxn, L, nsq, a.scale);   // MC = 10 + NIT: key tiles as the inner loop
-        else if (MC) b3_bwd_core_mfma<(MC > 0 && MC < 10 ? MC : 1)>(qkv, ob, dob, lses, dxn, L, nsq, a.scale);   // (the dy planes are dead since P2b: the wave-private tiles go there)
+        if (MC >= 10) b3_bwd_core_mfma_kt<(MC >= 10 ? MC % 10 : 1)>(qkv, ob, dob, lsd, dxn, L, nsq, a.scale);   // MC = 10 + NIT: key tiles as the inner loop
+        else if (MC) b3_bwd_core_mfma<(MC > 0 && MC < 10 ? MC : 1)>(qkv, ob, dob, lsd, dxn, L, nsq, a.scale);   // (the dy planes are dead since P2b: the wave-private tiles go there)
         for (int task = threadIdx.x; !MC && task < nqtasks; task += ATT_THREADS) {
             const int i = task % nq;
             const int h = (task / nq) % NH;
@@ -1324,15 +1339,15 @@ __global__ void __launch_bounds__(ATT_THREADS) attn_bwd3_kernel(AttnArgs a, Attn
             kv.load(opp, NDH);
             const float delta = go.dot(kv);
             dq.zero();
-            dlt[row_i * NH + h] = delta;
-            const float lse = lses[row_i * NH + h];
+            lsd[dlt_at(row_i * NH + h)] = delta;
+            const float lse = lsd[lse_at(row_i * NH + h)];
             const float* kbase = qkv + (size_t)(sq * L) * B3_LDQ + B3_I + ho;
             float* const prow = PH ? dxn + ((sq * NH + h) * L + i) * L : nullptr;     // P[(sequence, head)][query i][key j]
             for (int j = 0; j < L; ++j) {
                 const float* kp = kbase + (size_t)j * B3_LDQ;
-                kv.load(kp + B3_I, NDH);
+                kv.template load_lds<RD>(kp + B3_I, NDH);
                 const float dp = go.dot(kv);
-                kv.load(kp, NDH);
+                kv.template load_lds<RD>(kp, NDH);
                 const float p = rat_exp2(q.dot(kv) * sl2 - lse);
                 if (PH) prow[j] = p;
                 dq.axpy(p * (dp - delta), kv);
@@ -1363,14 +1378,17 @@ __global__ void __launch_bounds__(ATT_THREADS) attn_bwd3_kernel(AttnArgs a, Attn
             dv.zero();
             for (int i = 0; i < nq; ++i) {
                 const int row_i = sq * L + i;
-                t.load(dob + (size_t)row_i * B3_LDT + ho, NDH);
+                t.template load_lds<RD>(dob + (size_t)row_i * B3_LDT + ho, NDH);
                 const float dp = t.dot(vv);
-                const float delta = dlt[row_i * NH + h];
+                float2 ld;                                                   // {lse, delta}
+                if (LSD2) ld = *reinterpret_cast<const float2*>(lsd + 2 * (row_i * NH + h));
+                else ld = make_float2(PH ? 0.f : lsd[lse_at(row_i * NH + h)], lsd[dlt_at(row_i * NH + h)]);
+                const float delta = ld.y;
                 HV qv;
-                qv.load(qkv + (size_t)row_i * B3_LDQ + ho, NDH);
+                qv.template load_lds<RD>(qkv + (size_t)row_i * B3_LDQ + ho, NDH);
                 float p;
                 if (PH) p = dxn[((sq * NH + h) * L + i) * L + j];           // consecutive lanes = consecutive keys: conflict-free
-                else p = rat_exp2(qv.dot(kk) * sl2 - lses[row_i * NH + h]);
+                else p = rat_exp2(qv.dot(kk) * sl2 - ld.x);
                 dv.axpy(p, t);
                 dk.axpy(p * (dp - delta), qv);
             }
