@@ -860,6 +860,22 @@ int rat_topn_seg(const float* y, const int64_t* first_row, int64_t B, int n, int
 int rat_candidates_expand(const int32_t* ctx, const int32_t* cand, const int32_t* cols, const int64_t* first_row, int64_t B, int L,
                           int W, int32_t* out, void* stream);
 
+/* Every request's WHOLE ranking on the device (csrc/rank.hip; rat_amd/online.py: rank_requests, rank_candidates) — rat_topn_seg
+ * returns a page of n <= RAT_MAX_TOPN, this the full order.  first_row, f, heads and segments as above; row b is a MEMBER of segment h
+ * iff h is a head and h <= b < e.  Segments are disjoint; for valid first_row every row is a member of its request's segment.
+ *
+ * rat_rank_seg: y fp32 [B] -> out_order int32 [B], out_val fp32 [B], out_rank int32 [B].  For a member b of segment h:
+ *   out_rank[b] = the number of members of the segment that come before b in rat_topn_seg's total order — a before b iff
+ *   y[a] > y[b], or neither compares greater and a < b; a NaN after every number, NaNs among themselves by position, -0.0 and +0.0
+ *   tie: np.argsort(-y[h:e], kind="stable") for any input; out_order[h + out_rank[b]] = b - h, the position inside the segment;
+ *   out_val[h + i] = y[h + out_order[h + i]], the same bits (y is only compared).  A row that is a member of no segment gets
+ *   -1 / 0.0 / -1.  Every output element is written by every launch; the result is a function of the inputs alone.
+ * Any segment length is served.  One launch on `stream`, no atomics, no workspace, nothing allocated, synchronised or read back; NO
+ * content of first_row leads to an address outside the four buffers.  -1 + rat_last_error() on a null pointer, B < 1 or
+ * B > 2^31 - 1; nothing is launched then. */
+int rat_rank_seg(const float* y, const int64_t* first_row, int64_t B, int32_t* out_order, float* out_val, int32_t* out_rank,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,12 @@ and of the replayed top_candidates chain (its captured graph, device events), an
 plus reading pos, y and lens back against the way without it — the rows expanded on the host, uploaded, a replayed score_requests, all
 predictions read back and a numpy stable top-n per request — host clock + synchronise, the sides alternating round by round, results
 compared before anything is timed; (iii) the bytes both ways move per call, derived from the shapes.
+--rank — each request's full ranking instead (profiles/online/rank_bench.txt), same geometry and grid plus one request of 4096 rows:
+(i) device time per call of rat_rank_seg alone, with rat_topn_seg at n = 64 beside it (hipGraphs of REPS calls, device events, the two
+alternating), against the replayed rank_requests chain; (ii) a replayed rank_requests call — once with order, val and rank read back, once
+with the ranking left on the device — against the host way: replayed score_requests, every prediction read back, one
+np.argsort(-y_r, kind="stable") per request — host clock + synchronise, the sides alternating round by round, results compared before
+anything is timed; (iii) the bytes the ways move per call, derived from the shapes.
 There is no CPU fallback: without a GPU the tool exits with an error."""
 import argparse
 import os
@@ -885,6 +891,98 @@ def part_top(emit, quick):
     emit("   (%d ranked-candidate graphs, %d bucket graphs)" % (len(scorer._top_cand_graphs), len(scorer._bucket_graphs)))
 
 
+def part_rank(emit, quick):
+    from rat_amd import ops
+    from rat_amd.online import OnlineScorer, _first_rows
+    name, model, rows, vocab, cfg, n_pool, _capacity = _movielens(quick)
+    dev = torch.device("cuda:0")
+    min_s = 0.05 if quick else MIN_TIMED_MS / 1e3
+    pool = rows(n_pool)
+    rs = np.random.RandomState(7)
+    scorer = OnlineScorer(model, pool, cfg, graph=True)
+    L, n_top, cols = len(vocab), RANK_TOPN, [1]                             # the candidates of a request differ in the item column
+    grid = [(R, C) for R in ((1, 16) if quick else (1, 16, 64)) for C in (64, 256, 1024) if R * C <= scorer.graph_max_batch]
+    grid.append((1, scorer.graph_max_batch))
+    emit("== rank: %s, %d-row pool, requests of C_r candidate rows (one context, the candidates differ in column %s); the --top grid "
+         "and one request of graph_max_batch = %d rows" % (name, n_pool, cols, scorer.graph_max_batch))
+
+    def point(R, C_r):
+        C = R * C_r
+        ids = np.repeat(np.stack([rs.randint(0, v, size=R) for v in vocab], axis=1).astype(np.int32), C_r, axis=0)
+        ids[:, cols] = np.stack([rs.randint(0, vocab[c], size=C) for c in cols], axis=1)
+        return C, ids, (np.arange(R + 1) * C_r).astype(np.int64)
+
+    def host_way(ids, off):
+        """what a caller does without the call: score, read every prediction back, one numpy stable sort per request"""
+        y = scorer.score_requests((ids, off))[0].cpu().numpy()
+        order, val, rank = np.empty(len(y), np.int32), np.empty(len(y), np.float32), np.empty(len(y), np.int32)
+        for a, b in zip(off[:-1], off[1:]):
+            o = np.argsort(-y[a:b], kind="stable")
+            order[a:b], val[a:b] = o, y[a:b][o]
+            rank[a:b][o] = np.arange(b - a)
+        return order, val, rank
+
+    def ranked_way(ids, off):
+        r = scorer.rank_requests((ids, off))
+        return r.order.cpu().numpy(), r.val.cpu().numpy(), r.rank.cpu().numpy()
+
+    def ranked_resident(ids, off):
+        """the ranking stays where its consumer is: nothing is read back"""
+        r = scorer.rank_requests((ids, off))
+        torch.cuda.synchronize()
+        return r
+
+    results = []
+    for R, C_r in grid:
+        C, ids, off = point(R, C_r)
+        for _ in range(scorer.graph_warmup + 2):
+            got = ranked_way(ids, off)
+            want = host_way(ids, off)
+        torch.cuda.synchronize()
+        P = 1 << (C - 1).bit_length()
+        chain = [e[1] for k, e in scorer._rank_graphs.items() if k[0] == P]
+        assert len(chain) == 1 and chain[0], "the fully ranked chain of %d rows was not captured" % P
+        same = all(np.array_equal(g.view(np.int32), w.view(np.int32)) for g, w in zip(got, want))
+        # (i) the kernels alone against the replayed chain, device events
+        y = torch.from_numpy(rs.rand(P).astype(np.float32)).to(dev)
+        first = _first_rows(off, None, C, dev, pad_to=P)
+        alone = {"rank": _graph_of(lambda: ops.rank_seg(y, first), REPS)[0], "topn": _graph_of(lambda: ops.topn_seg(y, first, n_top), REPS)[0]}
+        t_alone = {k: v * 1e3 for k, v in time_alternating(alone, REPS, 50.0 if quick else 200.0).items()}
+        t_chain = time_alternating({"c": chain[0].graph}, 1, 50.0 if quick else 200.0)["c"] * 1e3
+        # (ii) the ways, host clock, alternating
+        per = {"ranked": [], "resident": [], "host": []}
+        while min(sum(v) for v in per.values()) / 1e6 < min_s or min(len(v) for v in per.values()) < 5:
+            for label, fn in (("ranked", ranked_way), ("resident", ranked_resident), ("host", host_way)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    fn(ids, off)
+                per[label].append((time.perf_counter() - t0) / 10 * 1e6)
+        results.append((R, C_r, C, P, t_alone, t_chain, per, same))
+    emit("== rank (i): device time per call [us]: rat_rank_seg alone and rat_topn_seg at n = %d alone (hipGraphs of %d calls over P rows, "
+         "device events, alternating) and the replayed rank_requests chain (prepare -> scan -> assemble -> forward -> rank; its captured "
+         "graph, device events)" % (n_top, REPS))
+    for R, C_r, C, P, t_alone, t_chain, per, same in results:
+        emit("R %3d x C_r %4d (P %4d) | rat_rank_seg %.1f | rat_topn_seg(n = %d) %.1f | rank / topn = %.2f | chain %.1f | share %.2f %%"
+             % (R, C_r, P, t_alone["rank"], n_top, t_alone["topn"], t_alone["rank"] / t_alone["topn"], t_chain, 100.0 * t_alone["rank"] / t_chain))
+    emit("== rank (ii): one call [us], host clock: replayed rank_requests + order, val and rank read back (ranked), the same with the "
+         "ranking left on the device and one synchronise (resident), against replayed score_requests + all predictions read back + "
+         "np.argsort(-y_r, kind=\"stable\") per request (host); rounds of 10 calls alternating; mean (min .. max over the rounds)")
+    for R, C_r, C, P, t_alone, t_chain, per, same in results:
+        a, c, b = (sum(per[k]) / len(per[k]) for k in ("ranked", "resident", "host"))
+        emit("R %3d x C_r %4d | ranked %s | resident %s | host %s | host / ranked = %.2fx | host / resident = %.2fx | results equal bit for bit: %s"
+             % (R, C_r, _stats(per["ranked"]), _stats(per["resident"]), _stats(per["host"]), b / a, b / c, same))
+    emit("== rank (iii): bytes per call, derived from the shapes (L = %d; every way uploads C L ids, and first_row, 8 P bytes, when the "
+         "request sizes changed since the last call)" % L)
+    for R, C_r, C, P, _a, _c, _per, _same in results:
+        emit("R %3d x C_r %4d | H2D %8d (C L ids) every way | D2H ranked %6d (order, val, rank: 12 C)  resident %d  host %6d (4 C)"
+             % (R, C_r, 4 * C * L, 12 * C, 0, 4 * C))
+    emit("   (%d fully-ranked graphs, %d bucket graphs)" % (len(scorer._rank_graphs), len(scorer._bucket_graphs)))
+
+
+RANK_TOPN = 64                                                              # rat_topn_seg's largest page, beside the full ranking
+
+
 class _SameSide:
     """score(ids, same=) behind the name _replay_round calls"""
 
@@ -911,6 +1009,7 @@ def main():
     ap.add_argument("--rows", action="store_true", help="measure the pool that looks at itself (horizon scan against the plain scan; score_rows)")
     ap.add_argument("--same", action="store_true", help="measure neighbours restricted to equal columns (the chain against the plain scan; score(same=))")
     ap.add_argument("--top", action="store_true", help="measure each request's top-n candidates (rat_topn_seg alone; top_candidates against the host way)")
+    ap.add_argument("--rank", action="store_true", help="measure each request's full ranking (rat_rank_seg alone; rank_requests against the host way)")
     ap.add_argument("--trace", action="store_true", help="with --delete: only a few deletions per point, for a kernel trace")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -948,6 +1047,9 @@ def main():
         return
     if args.top:
         part_top(emit, args.quick)
+        return
+    if args.rank:
+        part_rank(emit, args.quick)
         return
     part1(emit, args.quick)
     part2(emit, args.quick)

@@ -187,6 +187,8 @@ _SIGNATURES = {
     # the end of a request: each request's n best candidates, and the candidates' rows built from one context row per request
     "rat_topn_seg": (c_int, [_P, _P, c_int64, c_int, _P, _P, _P, _P]),
     "rat_candidates_expand": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, _P, _P]),
+    # ... and each request's whole ranking: order, values and every row's place
+    "rat_rank_seg": (c_int, [_P, _P, c_int64, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

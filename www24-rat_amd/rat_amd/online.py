@@ -90,11 +90,19 @@ come down instead of 4 C.  With ``graph=True`` the padding rule is ``score_reque
 of their own (``_top_graphs`` by bucket and n, ``_top_cand_graphs`` by the columns as well); the older calls and their graphs are
 untouched.  No ``same=`` / ``before=`` on these calls.
 
+A request can also end with its WHOLE order, for a re-ranker behind the model, rules that walk down the list, deeper pages or rank metrics:
+``rank_requests(requests)`` and ``rank_candidates(contexts, candidates, cols, request_offsets)`` take what ``top_requests`` /
+``top_candidates`` take, without n, run the same chains with ``rat_rank_seg`` in ``rat_topn_seg``'s place, and return
+``Ranking(order, val, rank, offsets, y_pred)``: ``order[o_r:o_{r+1}]`` is ``np.argsort(-y_r, kind="stable")``, ``val`` those predictions
+bit for bit, ``rank`` every row's place in its request — device tensors of B entries, any request length, nothing read back.  Their
+captured chains live in ``_rank_graphs`` / ``_rank_cand_graphs``; n > 64 on ``top_*`` stays refused.
+
 Not served online (refused at construction): the config keys ``exact_match_cols`` / ``exact_match_col_indices`` (the restriction is
 per call, ``same=``; not built: ``same`` with ``request_offsets``, and all used columns exact), label-wise retrieval, topK > 32, more
 than 32 retrieval columns, data-parallel models.  Rows are deleted from a
 ``window=True`` pool only: the append-only form reserves its IDF tables for the rows that can still come, which deletions would undo.
 """
+import collections
 import logging
 
 import numpy as np
@@ -107,6 +115,9 @@ from .data import DeviceBatch
 MAX_TOPK = 32
 MAX_COLS = 32
 MAX_TOPN = ops.MAX_TOPN          # candidates returned per request: a page of results
+
+# what rank_requests / rank_candidates return: device tensors over the caller's B rows (y_pred: None unless scores=True)
+Ranking = collections.namedtuple("Ranking", "order val rank offsets y_pred")
 
 
 def _as_device_ids(ids, device):
@@ -729,6 +740,25 @@ class _TopCandGraph(_ChainGraph, _HeadRows):
         return self.y_pred
 
 
+class _RankGraph(_BucketGraph):
+    """the request chain for P rows followed by rat_rank_seg: ids and first_row are the static inputs; ``run`` returns the static
+    (order [P], val [P], rank [P], y_pred [P]), uncloned"""
+
+    def __init__(self, scorer, ids, first_row):
+        _ChainGraph.__init__(self, scorer._rank_eager, ids, first_row)
+        self._first_host = None
+
+
+class _RankCandGraph(_TopCandGraph):
+    """rat_candidates_expand -> the request chain -> rat_rank_seg for P candidate rows and one tuple of candidate columns; inputs and
+    ``run`` are ``_TopCandGraph``'s"""
+
+    def __init__(self, scorer, cols_dev, slab, cand, first_row):
+        _ChainGraph.__init__(self, lambda s, c, f: scorer._rank_cand_eager(s, c, cols_dev, f), slab, cand, first_row)
+        self._cols = cols_dev
+        self._first_host = None
+
+
 class OnlineScorer:
     """``score(ids)``: fp32 [B] predictions of a trained model for fresh encoded rows ``ids`` [B, L], the neighbours retrieved from
     ``pool_array`` ([N, L + 1], label last) on the spot.  ``retrieval_configs`` is the dataset's block (``topK``, ``used_cols`` or
@@ -777,7 +807,9 @@ class OnlineScorer:
         self._same_rows_graphs = {}    # score_rows(indices, same=): the same for _RowsGraph
         self._top_graphs = {}          # top_requests: (bucket, n, ...) -> [eager calls seen, _TopGraph | False | None]
         self._top_cand_graphs = {}     # top_candidates: (bucket, n, ..., the candidate columns) -> [eager calls seen, _TopCandGraph | False | None]
-        self._cols_dev = {}            # top_candidates: the candidate columns as a tuple -> the same as an int32 device tensor
+        self._rank_graphs = {}         # rank_requests: (bucket, ...) -> [eager calls seen, _RankGraph | False | None]
+        self._rank_cand_graphs = {}    # rank_candidates: (bucket, ..., the candidate columns) -> [eager calls seen, _RankCandGraph | False | None]
+        self._cols_dev = {}            # top_candidates / rank_candidates: the candidate columns as a tuple -> the same as an int32 device tensor
         self._found = None             # relabel_where's index list (one entry per row the pool can hold), from its first call on
 
     # ------------------------------------------------------------------------------------------------------------------
@@ -1242,3 +1274,77 @@ class OnlineScorer:
                 heads = self._on_device(heads)
                 out = self._top_cand_eager(self._slab(contexts, heads, P), cand, cols_dev, self._on_device(first_row), n)
             return self._top_result(out, heads[:-1] if P > C else heads, C, scores)
+
+    # ---- each request's full ranking ---------------------------------------------------------------------------------------------
+    def _rank_eager(self, ids, first_row):
+        """the request chain, then rat_rank_seg over its predictions -> (order [B], val [B], rank [B], y_pred [B])"""
+        y_pred = self._score_eager(ids, first_row).contiguous()
+        return ops.rank_seg(y_pred, first_row, lib=self._lib) + (y_pred,)
+
+    def _rank_cand_eager(self, slab, cand, cols_dev, first_row):
+        return self._rank_eager(ops.candidates_expand(slab, cand, cols_dev, first_row, lib=self._lib), first_row)
+
+    @staticmethod
+    def _rank_result(out, B, offsets, scores):
+        order, val, rank = (t[:B].clone() for t in out[:3])                   # new tensors, not the graph's buffers; a pad request lies behind B
+        return Ranking(order, val, rank, offsets, out[3][:B].clone() if scores else None)
+
+    def rank_requests(self, requests, scores=False):
+        """The whole order of every request: ``requests`` as ``score_requests`` takes them -> ``Ranking(order, val, rank, offsets,
+        y_pred)`` of device tensors over the B rows: for request r, ``order[off[r]:off[r + 1]]`` are the positions INSIDE the request,
+        best first — ``np.argsort(-y_r, kind="stable")``: equal predictions in input order, a NaN last —, ``val`` those predictions bit
+        for bit, ``rank[b]`` row b's place in its request (``order[off[r] + rank[b]] == b - off[r]``); ``offsets`` as
+        ``score_requests`` returns them; ``y_pred`` the unsorted fp32 [B] when ``scores=True``, else None.  Any request length.  The
+        launches are ``score_requests``' chain, then ``rat_rank_seg`` — nothing is read back (device offsets are used unread).  With
+        ``graph=True`` the padding rule of ``score_requests`` holds, and a bucket's chain is captured after ``graph_warmup`` eager
+        calls into ``_rank_graphs`` (at most ``graph_sizes`` buckets; others stay eager)."""
+        if self.model.training:
+            raise RuntimeError("OnlineScorer.rank_requests needs the model in eval mode (model.eval())")
+        ids, off_host, off_dev = self._requests(requests)
+        B = ids.shape[0]
+        offsets = torch.from_numpy(off_host) if off_host is not None else off_dev
+        with torch.no_grad():
+            P = 1 << (B - 1).bit_length()
+            if not (self.graph and ids.is_cuda and P <= self.graph_max_batch):
+                return self._rank_result(self._rank_eager(ids, _first_rows(off_host, off_dev, B, self.device)), B, offsets, scores)
+            first_row = _first_rows(off_host, off_dev, B, self.device, pad_to=P, upload=False)
+            if P > B:                                                          # the pad rows: valid ids, a request of their own
+                ids = torch.cat([ids, ids[:1].expand(P - B, -1)])
+            key = (P, self.model._eval_graph_key((P, self.index.topK + 1, ids.shape[1])))
+            g = self._captured(self._rank_graphs, key, lambda: _RankGraph(self, ids, self._on_device(first_row)),
+                               "the fully ranked online requests", self.graph_sizes)
+            out = g.run(ids, first_row) if g is not None else self._rank_eager(ids, self._on_device(first_row))
+            return self._rank_result(out, B, offsets, scores)
+
+    def rank_candidates(self, contexts, candidates, cols, request_offsets, scores=False):
+        """``rank_requests`` for requests given as ``top_candidates`` takes them — ONE context row each (``contexts`` [R, L]) plus the
+        columns ``cols`` in which their candidates differ (``candidates`` [C, W], ``request_offsets`` [R + 1] over the candidates) —
+        without n: ``rat_candidates_expand`` after one indexed copy of the contexts, then ``rank_requests``' chain.  Returns what
+        ``rank_requests`` returns, positions counting the candidates of a request from 0.  With ``graph=True`` the chain of a
+        (bucket, cols) pair is captured into ``_rank_cand_graphs``."""
+        if self.model.training:
+            raise RuntimeError("OnlineScorer.rank_candidates needs the model in eval mode (model.eval())")
+        contexts, cand, cols, cols_dev, off_host, off_dev = self._candidates(contexts, candidates, cols, request_offsets)
+        C = cand.shape[0]
+        offsets = torch.from_numpy(off_host) if off_host is not None else off_dev
+        with torch.no_grad():
+            P = 1 << (C - 1).bit_length()
+            if not (self.graph and cand.is_cuda and P <= self.graph_max_batch):
+                slab = self._slab(contexts, self._heads(off_host, off_dev, C, False), C)
+                out = self._rank_cand_eager(slab, cand, cols_dev, _first_rows(off_host, off_dev, C, self.device))
+                return self._rank_result(out, C, offsets, scores)
+            first_row = _first_rows(off_host, off_dev, C, self.device, pad_to=P, upload=False)
+            heads = self._heads(off_host, off_dev, C, P > C, upload=False)
+            if P > C:                                                          # the pad request: the first request's context, copies of its first candidate
+                contexts = torch.cat([contexts, contexts[:1]])
+                cand = torch.cat([cand, cand[:1].expand(P - C, -1)])
+            key = (P, self.model._eval_graph_key((P, self.index.topK + 1, contexts.shape[1])), cols)
+            g = self._captured(self._rank_cand_graphs, key,
+                               lambda: _RankCandGraph(self, cols_dev, self._slab(contexts, self._on_device(heads), P), cand,
+                                                      self._on_device(first_row)),
+                               "the fully ranked candidate requests", self.graph_sizes)
+            if g is not None:
+                out = g.run(contexts, heads, cand, first_row)
+            else:
+                out = self._rank_cand_eager(self._slab(contexts, self._on_device(heads), P), cand, cols_dev, self._on_device(first_row))
+            return self._rank_result(out, C, offsets, scores)

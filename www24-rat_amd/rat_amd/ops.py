@@ -1272,3 +1272,25 @@ def candidates_expand(ctx, cand, cols, first_row, lib=None):
     out = torch.empty((B, L), dtype=torch.int32, device=dev)
     lib.call("rat_candidates_expand", _p(ctx), _p(cand), _p(cols), _p(first_row), B, L, W, _p(out), _stream(ctx))
     return out
+
+
+RANK_ROWS, RANK_TILE = 256, 1024                       # csrc/rank.hip: RK_THREADS rows per work-group, RK_TILE rows per LDS tile
+
+
+def rank_seg(y, first_row, lib=None):
+    """-> (order int32 [B], val fp32 [B], rank int32 [B]) on the inputs' device, nothing read back: every request's whole ranking.
+    For the request that opens at row h and ends before row e (first_row int64 [B]: for every row the row that opens its request),
+    order[h:e] = np.argsort(-y[h:e], kind="stable") — positions inside the request, best first; equal values in input order, a NaN
+    last —, val[h:e] = y[h:e][order[h:e]] bit for bit, and rank[b] is row b's place in its request: order[h + rank[b]] == b - h.  A row
+    of no request: -1 / 0.0 / -1.  Any request length (include/rat_hip.h: rat_rank_seg)."""
+    lib = lib or get_lib()
+    _chk(y, name="y")
+    if y.ndim != 1 or y.numel() < 1:
+        raise ValueError("rank_seg takes a non-empty 1-D vector y, got shape %s" % (tuple(y.shape),))
+    B, dev = y.numel(), y.device
+    _first_row_arg(first_row, B, dev, "rank_seg")
+    order = torch.empty((B,), dtype=torch.int32, device=dev)
+    val = torch.empty((B,), dtype=torch.float32, device=dev)
+    rank = torch.empty((B,), dtype=torch.int32, device=dev)
+    lib.call("rat_rank_seg", _p(y), _p(first_row), B, _p(order), _p(val), _p(rank), _stream(y))
+    return order, val, rank
