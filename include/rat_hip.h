@@ -836,6 +836,27 @@ size_t rat_eval_metrics_workspace(int64_t n, int grouped);
 int rat_eval_metrics(const float* y_pred, const float* y_true, const int32_t* group, int64_t n, double* out, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* Ranking metrics on the device (csrc/rankmetrics.hip): NDCG@k, MRR@k and HitRate@k per group, as later FuxiCTR releases report them
+ * beside gAUC (the reference checked out beside this project has none of them).  y_pred, y_true: fp32 [n], every label 0 or 1; group:
+ * int32 [n], a sort key only — any int32 is legal; cutoffs: int32 [n_cutoffs] on the HOST, 1 <= n_cutoffs <= 8, 1 <= k <= 2^31 - 1 (a
+ * cutoff k >= n means "no cutoff"); 1 <= n <= 2^31 - 1.  The caller owns every buffer; nothing is allocated, synchronised or read back.
+ *   Order inside a group: np.argsort(-p_g, kind="stable") over the group's rows in input order — descending prediction, ties keep input
+ *     order, -0.0 equal to +0.0 (the order rat_rank_seg documents).  A row's place r is 0-based.
+ *   Counted groups: a group counts if it holds at least one positive (y == 1); a group without one is skipped.  Each metric is the
+ *     unweighted mean over the counted groups.  For a counted group with P positives and f the place of its first positive:
+ *       DCG@k = sum_{r < k, y_r = 1} 1 / log2(r + 2)     IDCG@k = sum_{j < min(P, k)} 1 / log2(j + 2)     NDCG@k = DCG@k / IDCG@k
+ *       MRR@k = 1 / (f + 1) if f < k, else 0             HitRate@k = 1 if f < k, else 0.                   All arithmetic is float64.
+ *   out (float64 [n_cutoffs][8], device), per cutoff: [0] NDCG  [1] MRR  [2] HitRate = hits / counted, one division of two exact
+ *     integers  [3] groups counted  [4] groups seen  [5] hits, the counted groups with f < k  [6] k  [7] status bits: 1 a prediction is
+ *     NaN, 2 a label is neither 0 nor 1 (as in rat_eval_metrics), 16 no group holds a positive — any of them makes [0..2] NaN.
+ *   The sums run in sorted order through fixed trees and one bitwise-reproducible scan per call: the result is a function of the inputs
+ *   alone (of n and the sorted rows), not of scheduling; a row of out does not depend on the other cutoffs of the call.
+ * workspace: rat_eval_rank_metrics_workspace(n, n_cutoffs) bytes, 256-byte aligned.  -1 + rat_last_error() on a null pointer (group
+ * included), n or n_cutoffs out of range, a cutoff < 1, a workspace too small or misaligned; nothing is launched then. */
+size_t rat_eval_rank_metrics_workspace(int64_t n, int n_cutoffs);
+int rat_eval_rank_metrics(const float* y_pred, const float* y_true, const int32_t* group, int64_t n, const int32_t* cutoffs, int n_cutoffs,
+                          double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The end of a request on the device (csrc/topn.hip; rat_amd/online.py: top_requests, top_candidates): a request is one user with a
  * slate of candidates, and the caller wants the best n of them.  Both entry points take first_row (int64 [B], device) — for every
  * batch row the row that opens its request, what rat_bm25_query_prepare_seg takes — and use f(b) = clamp(first_row[b], 0, B - 1):

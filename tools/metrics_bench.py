@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Evaluation metrics: today's host path against the device chain, end to end.
 
-    python tools/metrics_bench.py [--sizes 100000,1000000,10000000] [--out FILE]
+    python tools/metrics_bench.py [--sizes 100000,1000000,10000000] [--out FILE] [--rank]
 
 For every N and every grouping (none, 10^4 groups, N / 10 groups), two sides over the SAME device vectors:
   (a) host  : the copy evaluate_generator makes (y_pred / y_true widened to float64 on the device, copied to the host; the group ids
@@ -9,6 +9,8 @@ For every N and every grouping (none, 10^4 groups, N / 10 groups), two sides ove
   (b) device: metrics.device_metrics — the launch chain of rat_eval_metrics plus its 64-byte read-back.
 Timed with the host clock around calls that end in a synchronise (side (a) ends in numpy, side (b) in the read-back; a
 torch.cuda.synchronize() follows both), the sides alternating in rounds; min, median and max of the per-call time over the rounds.
+--rank measures the ranking names instead: N / 10 groups, one cutoff (10) and four cutoffs (1, 5, 10, 50), every K with its three names
+NDCG(k=K), MRR(k=K), HitRate(k=K); (b) is then the launch chain of rat_eval_rank_metrics plus its 64-byte read-back per cutoff.
 No ratio is gated: the table is what was measured.  Needs a GPU: there is no fallback."""
 import argparse
 import logging
@@ -39,6 +41,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--budget", type=float, default=0.25, help="seconds of calls per side and round (at least one call)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--rank", action="store_true", help="the ranking names NDCG / MRR / HitRate instead of logloss / AUC / GAUC")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/metrics_bench.py measures on a GPU; none is visible")
@@ -54,9 +57,14 @@ def main():
         lines.append(line)
 
     for n in [int(x) for x in args.sizes.split(",")]:
-        for label, groups in (("ungrouped", None), ("10^4 groups", 10 ** 4), ("N/10 groups", n // 10)):
+        plans = [("ungrouped", None, None), ("10^4 groups", 10 ** 4, None), ("N/10 groups", n // 10, None)]
+        if args.rank:
+            plans = [("k = 10", n // 10, (10,)), ("k = 1,5,10,50", n // 10, (1, 5, 10, 50))]
+        for label, groups, cutoffs in plans:
             y_pred, y_true, group = make(n, groups, device)
             names = ["logloss", "AUC"] + ([] if group is None else ["GAUC"])
+            if cutoffs:
+                names = ["%s(k=%d)" % (kind, k) for k in cutoffs for kind in ("NDCG", "MRR", "HitRate")]
 
             def host():
                 yp = y_pred.double().cpu().numpy()
@@ -87,9 +95,14 @@ def main():
                     times[name].append(timed(fn, calls[name])[0] * 1e3)
             a, b = results["a"], results["b"]
             diffs = " ".join("%s %.3g" % (k, abs(a[k] - b[k])) for k in names)
+            if cutoffs:
+                diffs = "worst NDCG %.3g, MRR %.3g; HitRate equal: %s" % tuple(
+                    [max(abs(a[k] - b[k]) for k in names if k.startswith(kind)) for kind in ("NDCG", "MRR")]
+                    + [all(a[k] == b[k] for k in names if k.startswith("HitRate"))])
             fmt = lambda v: "%.3f / %.3f / %.3f" % (min(v), statistics.median(v), max(v))      # noqa: E731
-            emit("N %9d %-12s | (a) host %s (%d calls x %d rounds) | (b) device %s (%d calls x %d rounds) | |a - b|: %s | AUC equal: %s"
-                 % (n, label, fmt(times["a"]), calls["a"], args.rounds, fmt(times["b"]), calls["b"], args.rounds, diffs, a["AUC"] == b["AUC"]))
+            tail = "" if cutoffs else " | AUC equal: %s" % (a["AUC"] == b["AUC"])
+            emit("N %9d %-12s | (a) host %s (%d calls x %d rounds) | (b) device %s (%d calls x %d rounds) | |a - b|: %s%s"
+                 % (n, label, fmt(times["a"]), calls["a"], args.rounds, fmt(times["b"]), calls["b"], args.rounds, diffs, tail))
             del y_pred, y_true, group
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -184,6 +184,9 @@ _SIGNATURES = {
     # evaluation metrics on the device: logloss, AUC and per-group GAUC of a prediction vector -> float64 [8]
     "rat_eval_metrics_workspace": (c_size_t, [c_int64, c_int]),
     "rat_eval_metrics": (c_int, [_P, _P, _P, c_int64, _P, _P, c_size_t, _P]),
+    # ranking metrics on the device: NDCG@k, MRR@k and HitRate@k per group -> float64 [n_cutoffs][8]
+    "rat_eval_rank_metrics_workspace": (c_size_t, [c_int64, c_int]),
+    "rat_eval_rank_metrics": (c_int, [_P, _P, _P, c_int64, _P, c_int, _P, _P, c_size_t, _P]),
     # the end of a request: each request's n best candidates, and the candidates' rows built from one context row per request
     "rat_topn_seg": (c_int, [_P, _P, c_int64, c_int, _P, _P, _P, _P]),
     "rat_candidates_expand": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, _P, _P]),

@@ -11,6 +11,7 @@ import torch
 from torch import nn
 
 from .metrics import device_metrics as evaluate_metrics_on_device
+from .metrics import is_grouped as is_grouped_metric
 from .metrics import evaluate_metrics
 
 
@@ -59,7 +60,8 @@ class BaseModel(nn.Module):
                  reduce_lr_on_plateau=True, embedding_initializer="torch.nn.init.normal_(std=1e-4)",
                  retrieval_augmented=False, retrieval_configs=None, device_metrics=False, group_id=None, **kwargs):
         """device_metrics: evaluate_generator computes its metrics on the device (metrics.device_metrics: 64 bytes come back instead of
-        every prediction and label).  group_id: the categorical feature whose id on the target row groups the rows for "GAUC"."""
+        every prediction and label).  group_id: the categorical feature whose id on the target row groups the rows for "GAUC" and the
+        ranking names "NDCG(k=K)", "MRR(k=K)", "HitRate(k=K)"."""
         super().__init__()
         self.device = get_device(gpu)
         self._monitor = Monitor(kv=monitor)
@@ -91,8 +93,9 @@ class BaseModel(nn.Module):
                 raise ValueError("group_id=%r is a %s field: GAUC groups by one id per row, so it takes a plain categorical field"
                                  % (group_id, spec["type"]))
             self._group_col = int(spec["index"])
-        if "GAUC" in (self._validation_metrics or []) and group_id is None:
-            raise ValueError('metrics holds "GAUC" but no group_id names the feature to group by')
+        for metric in (self._validation_metrics or []):
+            if is_grouped_metric(metric) and group_id is None:
+                raise ValueError('metrics holds "%s" but no group_id names the feature to group by' % metric)
         self._refuse_new_eval_options_under_dp()
         self._verbose = kwargs["verbose"]
         self._max_gradient_norm = 10.0
@@ -374,13 +377,13 @@ class BaseModel(nn.Module):
                              "exchanged.  Evaluate on one device, or drop the two options")
 
     def _evaluate_generator_options(self, data_generator):
-        """evaluate_generator with device_metrics and / or group_id: predictions, labels and (for "GAUC") the target rows' ids of the
+        """evaluate_generator with device_metrics and / or group_id: predictions, labels and (for "GAUC" and the ranking names) the target rows' ids of the
         group column stay on the device.  With device_metrics the metric chain runs there and 64 bytes come back; without, the three
         vectors are copied once and metrics.evaluate_metrics runs on the host as before."""
         self._refuse_new_eval_options_under_dp()
         self.eval()
         metrics = self._validation_metrics
-        col = self._group_col if "GAUC" in metrics else None
+        col = self._group_col if any(is_grouped_metric(m) for m in metrics) else None
         preds, trues, groups = [], [], []
         with torch.no_grad():
             for batch_data in data_generator:

@@ -1013,14 +1013,29 @@ class OnlineScorer:
         ids, labels, _before = ops.pool_gather_rows(self.pool_ids, self.pool_labels, idx, lib=self._lib, **self.index._pool_form())
         return y_pred, labels, (None if col is None else ids[:, col].contiguous())
 
-    def evaluate_rows(self, indices, same=None, group=None, device=False):
+    @staticmethod
+    def _cutoff_list(cutoffs, group, what):
+        """``cutoffs``: an iterable of positive integers (at most 8 for the raw tensor) -> a list; they need ``group``"""
+        ks = [k for k in cutoffs]
+        for k in ks:
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 1:
+                raise ValueError("%s: a cutoff is a positive integer, got %r" % (what, k))
+        if ks and group is None:
+            raise ValueError("%s: cutoffs rank the rows inside groups; name the id column with group=" % what)
+        return [int(k) for k in ks]
+
+    def evaluate_rows(self, indices, same=None, group=None, device=False, cutoffs=()):
         """{"logloss": ..., "AUC": ...} of ``score_rows(indices)`` against the rows' stored labels: how well the model does on the
         traffic in the window.  ``group=col`` (the index of one id column of the rows, e.g. the user's) adds "GAUC": the per-group AUC
-        weighted by the groups' rows.  By default ``metrics.evaluate_metrics`` runs on the host after one device-to-host copy of the
-        vectors; ``device=True`` runs the metric chain on the device (``metrics.device_metrics``) and copies 64 bytes."""
+        weighted by the groups' rows; every K in ``cutoffs`` (they need ``group``) adds "NDCG(k=K)", "MRR(k=K)" and "HitRate(k=K)", the
+        ranking metrics per group (rat_amd/metrics.py).  By default ``metrics.evaluate_metrics`` runs on the host after one
+        device-to-host copy of the vectors; ``device=True`` runs the metric chains on the device (``metrics.device_metrics``) and copies
+        64 bytes, plus 64 per cutoff."""
         from .metrics import device_metrics, evaluate_metrics
+        ks = self._cutoff_list(cutoffs, group, "evaluate_rows")
         y_pred, labels, gids = self._rows_vectors(indices, same, group, "evaluate_rows")
         names = ["logloss", "AUC"] + (["GAUC"] if gids is not None else [])
+        names += ["%s(k=%d)" % (kind, k) for k in ks for kind in ("NDCG", "MRR", "HitRate")]
         if device:
             return device_metrics(labels, y_pred, names, group_index=gids, lib=self._lib)
         both = torch.stack([y_pred, labels]).cpu().numpy()
@@ -1032,6 +1047,16 @@ class OnlineScorer:
         GAUC — NaN without ``group`` —, n_pos, n_neg, groups counted, their rows, status bits): nothing is read back, a monitor can collect many of them and copy once"""
         y_pred, labels, gids = self._rows_vectors(indices, same, group, "metrics_rows")
         return ops.eval_metrics(y_pred.contiguous(), labels, gids, lib=self._lib)
+
+    def rank_metrics_rows(self, indices, cutoffs, same=None, group=None):
+        """the raw float64 [m, 8] device tensor of ``ops.eval_rank_metrics`` over ``score_rows(indices)`` and the rows' stored labels inside
+        the groups of id column ``group`` — per cutoff NDCG, MRR, HitRate, groups counted, groups seen, hits, k, status bits: nothing is
+        read back"""
+        ks = self._cutoff_list(cutoffs, group, "rank_metrics_rows")
+        if group is None:
+            raise ValueError("rank_metrics_rows: name the id column that groups the rows with group=")
+        y_pred, labels, gids = self._rows_vectors(indices, same, group, "rank_metrics_rows")
+        return ops.eval_rank_metrics(y_pred.contiguous(), labels, gids, ks, lib=self._lib)
 
     def _graph_for(self, ids, same=None):
         """the captured chain of ``score(ids)``, or None: launch eagerly.  ``same``: a dictionary of its own, the key extended by the

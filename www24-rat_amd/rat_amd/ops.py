@@ -1216,6 +1216,41 @@ def eval_metrics(y_pred, y_true, group=None, lib=None):
     return out
 
 
+MAX_CUTOFFS = 8
+
+
+def eval_rank_metrics(y_pred, y_true, group, cutoffs, lib=None):
+    """-> float64 [m, 8] on the inputs' device, nothing read back: per cutoff {NDCG@k, MRR@k, HitRate@k, groups counted, groups seen,
+    hits, k, status bits} (include/rat_hip.h: rat_eval_rank_metrics) of y_pred fp32 [n] against y_true fp32 [n] inside the groups of
+    group int32 [n]; cutoffs: 1 <= m <= 8 host integers in [1, 2^31 - 1].  Status bits: 1 a NaN prediction, 2 a label that is neither 0
+    nor 1, 16 no group holds a positive — any of them makes the three metrics NaN."""
+    lib = lib or get_lib()
+    if group is None:
+        raise ValueError("eval_rank_metrics needs the group ids")
+    _chk(y_pred, name="y_pred"), _chk(y_true, name="y_true"), _chk(group, torch.int32, "group")
+    n = y_pred.numel()
+    if y_pred.ndim != 1 or tuple(y_true.shape) != (n,) or tuple(group.shape) != (n,):
+        raise ValueError("eval_rank_metrics takes 1-D vectors of one length")
+    dev = y_pred.device
+    if y_true.device != dev or group.device != dev:
+        raise ValueError("eval_rank_metrics: the vectors sit on different devices")
+    ks = [k for k in cutoffs]
+    if not 1 <= len(ks) <= MAX_CUTOFFS:
+        raise ValueError("eval_rank_metrics takes 1 to %d cutoffs, got %d" % (MAX_CUTOFFS, len(ks)))
+    for k in ks:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 2 ** 31 - 1:
+            raise ValueError("eval_rank_metrics: a cutoff is an integer in [1, 2^31 - 1], got %r" % (k,))
+    host_ks = (ctypes.c_int32 * len(ks))(*[int(k) for k in ks])
+    nbytes = lib.size("rat_eval_rank_metrics_workspace", n, len(ks))
+    ws = torch.empty((nbytes + 255) // 8 + 32, dtype=torch.int64, device=dev)
+    skip = (-ws.data_ptr() % 256) // 8                                           # the C ABI wants 256-byte alignment
+    ws = ws[skip:]
+    out = torch.empty((len(ks), 8), dtype=torch.float64, device=dev)
+    lib.call("rat_eval_rank_metrics", _p(y_pred), _p(y_true), _p(group), n, ctypes.cast(host_ks, ctypes.c_void_p), len(ks), _p(out),
+             _p(ws), nbytes, _stream(y_pred))
+    return out
+
+
 # ----------------------------------------------------------------------------- the end of a request (rat_amd/online.py)
 MAX_TOPN = 64                                          # RAT_MAX_TOPN
 
