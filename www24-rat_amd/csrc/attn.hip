@@ -348,6 +348,28 @@ __device__ __forceinline__ void store_rows_residual(float* dst, const float* til
     }
 }
 
+// A row of an LDS tile that a loop steps through: the 32-bit LDS address itself, the tile's base included, so that every read of the row is
+// one register plus an immediate offset.  rat_lds_row() hides the address from constant re-association: left to itself hipcc splits
+// `row + base + 8 c` of a tile that lies beyond the 16-bit offset field of a DS instruction (the dO tile of attn_bwd3_kernel) into the row
+// and one large literal per read, and spends an integer add per read on putting them together again.  (The host emulation: a plain pointer.)
+#if !defined(RAT_EMU)
+typedef const __attribute__((address_space(3))) float* RatLdsRow;
+__device__ __forceinline__ RatLdsRow rat_lds_row(const float* p) {
+    uint32_t a = (uint32_t)(uintptr_t)(RatLdsRow)p;
+    asm("" : "+v"(a));
+    return (RatLdsRow)(uintptr_t)a;
+}
+__device__ __forceinline__ float2 rat_lds_ld2(RatLdsRow p) {             // an 8-byte pair in one read
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const f32x2 t = *(const __attribute__((address_space(3))) f32x2*)p;
+    return make_float2(t.x, t.y);
+}
+#else
+typedef const float* RatLdsRow;
+__device__ __forceinline__ RatLdsRow rat_lds_row(const float* p) { return p; }
+__device__ __forceinline__ float2 rat_lds_ld2(RatLdsRow p) { return *reinterpret_cast<const float2*>(p); }
+#endif
+
 // per-head vectors of the attention core: compile-time dim_head (8-byte LDS accesses) or runtime <= DH_MAX
 template <int TDH>
 struct HeadVec {
@@ -374,6 +396,17 @@ struct HeadVec {
     __device__ __forceinline__ void load_lds(const float* p, int dh) {
 #if !defined(RAT_EMU)
         if (UNPAIRED && TDH > 0 && TDH % 2 == 0) {
+            load_lds<true>((RatLdsRow)p, dh);
+            return;
+        }
+#endif
+        load(p, dh);
+    }
+#if !defined(RAT_EMU)
+    // the same from a row that is held as its LDS address (RatLdsRow): N / 2 reads off one register, offset:0 ... 4 N - 8
+    template <bool UNPAIRED = true>
+    __device__ __forceinline__ void load_lds(RatLdsRow p, int dh) {
+        if (UNPAIRED && TDH > 0 && TDH % 2 == 0) {
             typedef float f32x2 __attribute__((ext_vector_type(2)));
             typedef const volatile __attribute__((address_space(3))) f32x2* lds_f32x2_ptr;
             const lds_f32x2_ptr q = (lds_f32x2_ptr)p;
@@ -385,9 +418,9 @@ struct HeadVec {
             }
             return;
         }
-#endif
-        load(p, dh);
+        load((const float*)p, dh);
     }
+#endif
     __device__ __forceinline__ void store(float* p, int dh, float scale) const {
         if (TDH > 0 && TDH % 2 == 0) {
 #pragma unroll

@@ -1327,9 +1327,10 @@ __global__ void __launch_bounds__(ATT_THREADS) attn_bwd3_kernel(AttnArgs a, Attn
         if (MC >= 10) b3_bwd_core_mfma_kt<(MC >= 10 ? MC % 10 : 1)>(qkv, ob, dob, lsd, dxn, L, nsq, a.scale);   // MC = 10 + NIT: key tiles as the inner loop
         else if (MC) b3_bwd_core_mfma<(MC > 0 && MC < 10 ? MC : 1)>(qkv, ob, dob, lsd, dxn, L, nsq, a.scale);   // (the dy planes are dead since P2b: the wave-private tiles go there)
         for (int task = threadIdx.x; !MC && task < nqtasks; task += ATT_THREADS) {
-            const int i = task % nq;
-            const int h = (task / nq) % NH;
-            const int sq = task / (nq * NH);
+            const unsigned th = (unsigned)task / (unsigned)nq;               // (sequence, head): one division, NH is a power of two
+            const int i = task - (int)th * nq;
+            const int h = (int)(th % NH);
+            const int sq = (int)(th / NH);
             const int row_i = sq * L + i;
             const int ho = h * NDH;
             float* opp = ob + (size_t)row_i * B3_LDT + ho;
@@ -1366,9 +1367,10 @@ __global__ void __launch_bounds__(ATT_THREADS) attn_bwd3_kernel(AttnArgs a, Attn
         __syncthreads();
         RAT_PROF_MARK(4);
         for (int task = threadIdx.x; !MC && task < ntasks; task += ATT_THREADS) {
-            const int j = task % L;
-            const int h = (task / L) % NH;
-            const int sq = task / (L * NH);
+            const unsigned th = (unsigned)task / (unsigned)L;
+            const int j = task - (int)th * L;
+            const int h = (int)(th % NH);
+            const int sq = (int)(th / NH);
             const int ho = h * NDH;
             float* kp = qkv + (size_t)(sq * L + j) * B3_LDQ + B3_I + ho;
             HV kk, vv, dk, dv, t;
@@ -1376,21 +1378,31 @@ __global__ void __launch_bounds__(ATT_THREADS) attn_bwd3_kernel(AttnArgs a, Attn
             vv.load(kp + B3_I, NDH);
             dk.zero();
             dv.zero();
+            // Query i's dO row, Q row and {lse, delta} (PH: its P row too) are stepped as LDS addresses that hold their tile's base
+            // (RatLdsRow): one add per row and trip, every read of a row off one register.  Indexed by row_i = sq L + i, the dO tile's
+            // reads — it lies past the 16-bit offset field — cost an add of a large literal each (12 integer adds per trip, now 3).
+            RatLdsRow dop = rat_lds_row(dob + (size_t)(sq * L) * B3_LDT + ho);
+            RatLdsRow qp = rat_lds_row(qkv + (size_t)(sq * L) * B3_LDQ + ho);
+            RatLdsRow lp = rat_lds_row(lsd + lse_at(sq * L * NH + h));       // LSD2: the pair; else lse here, delta ATT_ROWS NH floats on
+            RatLdsRow pp = rat_lds_row(PH ? dxn + (sq * NH + h) * L * L + j : dxn);   // P[(sequence, head)][query i][key j]
             for (int i = 0; i < nq; ++i) {
-                const int row_i = sq * L + i;
-                t.template load_lds<RD>(dob + (size_t)row_i * B3_LDT + ho, NDH);
+                t.template load_lds<RD>(dop, NDH);
                 const float dp = t.dot(vv);
                 float2 ld;                                                   // {lse, delta}
-                if (LSD2) ld = *reinterpret_cast<const float2*>(lsd + 2 * (row_i * NH + h));
-                else ld = make_float2(PH ? 0.f : lsd[lse_at(row_i * NH + h)], lsd[dlt_at(row_i * NH + h)]);
+                if (LSD2) ld = rat_lds_ld2(lp);
+                else ld = make_float2(PH ? 0.f : lp[0], lp[ATT_ROWS * NH]);
                 const float delta = ld.y;
                 HV qv;
-                qv.template load_lds<RD>(qkv + (size_t)row_i * B3_LDQ + ho, NDH);
+                qv.template load_lds<RD>(qp, NDH);
                 float p;
-                if (PH) p = dxn[((sq * NH + h) * L + i) * L + j];           // consecutive lanes = consecutive keys: conflict-free
+                if (PH) p = pp[0];                                          // consecutive lanes = consecutive keys: conflict-free
                 else p = rat_exp2(qv.dot(kk) * sl2 - ld.x);
                 dv.axpy(p, t);
                 dk.axpy(p * (dp - delta), qv);
+                dop += B3_LDT;
+                qp += B3_LDQ;
+                lp += LSD2 ? 2 * NH : NH;
+                if (PH) pp += L;
             }
             dk.store(kp, NDH, a.scale);
             dv.store(kp + B3_I, NDH, 1.0f);
