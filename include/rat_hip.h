@@ -897,6 +897,42 @@ int rat_candidates_expand(const int32_t* ctx, const int32_t* cand, const int32_t
 int rat_rank_seg(const float* y, const int64_t* first_row, int64_t B, int32_t* out_order, float* out_val, int32_t* out_rank,
                  void* stream);
 
+/* A device-resident item catalogue (csrc/catalogue.hip; rat_amd/online.py: set_catalogue, top_items, rank_items, top_catalogue):
+ * cat int32 [M][W] holds, for each of M items, the ids of the W columns `cols` of the encoded row, and a candidate is an INDEX into
+ * it.  first_row, f, heads and segments as rat_topn_seg documents them.  One launch each on `stream`, no atomics, nothing allocated,
+ * synchronised or read back; every output element is written by every launch; NO content of any argument — first_row, items, cols,
+ * heads, the lists and their offsets, the pages and their lengths, item0 — leads to an address outside the buffers (rows, items, heads,
+ * lengths and offsets are clamped before they index anything).  -1 + rat_last_error() on a null pointer, B, R or M < 1 (or > 2^31 - 1),
+ * L, W or n out of range, E < 0, rows_per_request < 1; nothing is launched then.
+ *
+ * rat_catalogue_expand: out[b][l] (int32 [B][L]) = cat[i(b)][w] where l == cols[w] (int32 [W], device; distinct, in [0, L) — an entry
+ *   outside is skipped), otherwise ctx[f(b)][l] (int32 [B][L]; head rows only are read).  items (int32 [B]) given:
+ *   i(b) = clamp(items[b], 0, M - 1).  items == NULL, the SWEEP form: i(b) = clamp(item0 + (b - f(b)), 0, M - 1) — the k-th row of a
+ *   request is catalogue item item0 + k.  1 <= L, W <= 8192.  16-byte accesses when L % 4 == 0 and ctx / out are 16-byte aligned.
+ *
+ * Exclusion lists: ex_items int32 [E], ex_offsets int64 [R + 1]; request r's list is ex_items[lo .. hi) with
+ *   lo = clamp(ex_offsets[r], 0, E), hi = clamp(ex_offsets[r + 1], lo, E).  It is ASCENDING and searched by lower bound: an unsorted
+ *   list gives a wrong answer but never a wrong address.  E == 0 allows ex_items == NULL.
+ *
+ * rat_topn_exclude: out_y[b] (fp32 [B]) = -inf when the catalogue item of row b, item0 + (b - f(b)), is in the list of request
+ *   r = clamp(f(b) / rows_per_request, 0, R - 1), otherwise y[b] with the same bits.
+ *
+ * rat_topn_merge: merges a chunk's page into the running page of each of R requests, IN PLACE.  Running page: run_item int32 [R][n],
+ *   run_val fp32 [R][n], run_len int32 [R] (clamped to [0, n]); the chunk's page: rat_topn_seg's pos / val / len ([B][n], [B][n],
+ *   [B]) read at row clamp(heads[r], 0, B - 1) (heads int64 [R]), an entry's item = item0 + pos.  Chunk entries whose item is in
+ *   request r's list are dropped first — by lookup, not by value; ex_items == NULL (then ex_offsets may be NULL too): nothing is
+ *   dropped.  The merged order is rat_topn_seg's total order over (value, item): a before b iff val[a] > val[b], or neither compares
+ *   greater and a stands first — a running entry before a chunk entry (a sweep visits items in ascending order), inside a page the
+ *   lower slot; a NaN after every number, -0.0 ties with +0.0.  The first n survive, run_len = min(n, entries kept), the tail is
+ *   -1 / 0.0.  Values are moved, never computed with.  1 <= n <= RAT_MAX_TOPN. */
+int rat_catalogue_expand(const int32_t* ctx, const int32_t* cat, const int32_t* items, int64_t item0, const int32_t* cols,
+                         const int64_t* first_row, int64_t B, int L, int W, int64_t M, int32_t* out, void* stream);
+int rat_topn_exclude(const float* y, const int64_t* first_row, int64_t item0, int64_t rows_per_request, const int32_t* ex_items,
+                     const int64_t* ex_offsets, int64_t E, int64_t R, int64_t B, float* out_y, void* stream);
+int rat_topn_merge(int32_t* run_item, float* run_val, int32_t* run_len, const int32_t* pos, const float* val, const int32_t* len,
+                   const int64_t* heads, int64_t item0, const int32_t* ex_items, const int64_t* ex_offsets, int64_t E, int64_t R,
+                   int64_t B, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

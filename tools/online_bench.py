@@ -59,6 +59,11 @@ alternating), against the replayed rank_requests chain; (ii) a replayed rank_req
 with the ranking left on the device — against the host way: replayed score_requests, every prediction read back, one
 np.argsort(-y_r, kind="stable") per request — host clock + synchronise, the sides alternating round by round, results compared before
 anything is timed; (iii) the bytes the ways move per call, derived from the shapes.
+--catalogue — the best n of a whole resident item catalogue instead (profiles/online/catalogue_bench.txt), same geometry, the immutable
+pool, R in {1, 16} users against all M in {4096, 65536} items (the items differ in the item column), n = 10, chunk = graph_max_batch // R:
+(i) a top_catalogue call plus reading items, y and lens back against the host loop — per chunk the rows expanded on the host, uploaded, a
+replayed score_requests, all predictions read back, a numpy merge — host clock + synchronise, one call per round, the sides alternating,
+results compared before anything is timed; (ii) the bytes both ways move per call, derived from the shapes.
 There is no CPU fallback: without a GPU the tool exits with an error."""
 import argparse
 import os
@@ -980,6 +985,75 @@ def part_rank(emit, quick):
     emit("   (%d fully-ranked graphs, %d bucket graphs)" % (len(scorer._rank_graphs), len(scorer._bucket_graphs)))
 
 
+def part_catalogue(emit, quick):
+    from rat_amd.online import OnlineScorer
+    name, model, rows, vocab, cfg, n_pool, _capacity = _movielens(quick)
+    min_s = 0.05 if quick else MIN_TIMED_MS / 1e3
+    pool = rows(n_pool)
+    rs = np.random.RandomState(11)
+    scorer = OnlineScorer(model, pool, cfg, graph=True)
+    L, n, cols = len(vocab), 10, [1]                                        # the items of the catalogue differ in the item column
+    W = len(cols)
+    grid = [(M, R) for M in ((4096,) if quick else (4096, 65536)) for R in (1, 16)]
+    emit("== catalogue: %s, %d-row pool, R users against ALL M items of a resident catalogue (column %s), n = %d, chunk = graph_max_batch // R "
+         "= %d // R items per request per pass" % (name, n_pool, cols, n, scorer.graph_max_batch))
+
+    def host_way(contexts, cat, chunk):
+        """what a caller does without the catalogue: per chunk expand on the host, upload, score, read the predictions back, merge in numpy"""
+        R, M = len(contexts), len(cat)
+        items = np.full((R, n), -1, dtype=np.int32)
+        val = np.zeros((R, n), dtype=np.float32)
+        lens = np.zeros(R, dtype=np.int32)
+        for i0 in range(0, M, chunk):
+            m = min(chunk, M - i0)
+            ids = np.repeat(contexts, m, axis=0)
+            ids[:, cols] = np.tile(cat[i0:i0 + m], (R, 1))
+            y = scorer.score_requests((ids, np.arange(R + 1, dtype=np.int64) * m))[0].cpu().numpy().reshape(R, m)
+            for r in range(R):
+                v = np.concatenate([val[r, :lens[r]], y[r]])
+                i = np.concatenate([items[r, :lens[r]], np.arange(i0, i0 + m, dtype=np.int32)])
+                order = np.argsort(-v, kind="stable")[:n]
+                items[r, :len(order)], val[r, :len(order)], lens[r] = i[order], v[order], len(order)
+        return items, val, lens
+
+    def catalogue_way(contexts, _cat, chunk):
+        items, val, lens = scorer.top_catalogue(contexts, n, chunk=chunk)
+        return items.cpu().numpy(), val.cpu().numpy(), lens.cpu().numpy()
+
+    results = []
+    for M, R in grid:
+        chunk = min(max(1, scorer.graph_max_batch // R), M)
+        contexts = np.stack([rs.randint(0, v, size=R) for v in vocab], axis=1).astype(np.int32)
+        cat = np.stack([rs.randint(0, vocab[c], size=M) for c in cols], axis=1).astype(np.int32)
+        scorer.set_catalogue(cat, cols)
+        for _ in range(scorer.graph_warmup + 1):
+            got = catalogue_way(contexts, cat, chunk)
+            want = host_way(contexts, cat, chunk)
+        torch.cuda.synchronize()
+        same = all(np.array_equal(g.view(np.int32), w.view(np.int32)) for g, w in zip(got, want))
+        per = {"catalogue": [], "host": []}
+        while min(sum(v) for v in per.values()) / 1e6 < min_s or min(len(v) for v in per.values()) < 3:
+            for label, fn in (("catalogue", catalogue_way), ("host", host_way)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn(contexts, cat, chunk)
+                per[label].append((time.perf_counter() - t0) * 1e6)
+        results.append((M, R, chunk, per, same))
+    emit("== catalogue (i): one call [us], host clock: top_catalogue (per pass sweep expansion -> replayed score_requests -> rat_topn_seg -> "
+         "rat_topn_merge, eager around the bucket graph) + items, y and lens read back, against the host loop: per chunk host expansion + "
+         "upload + replayed score_requests + all predictions read back + numpy merge; one call per round, alternating; mean (min .. max)")
+    for M, R, chunk, per, same in results:
+        a, b = (sum(per[k]) / len(per[k]) for k in ("catalogue", "host"))
+        emit("M %5d x R %2d (%3d passes of %4d) | catalogue %s | host %s | host / catalogue = %.2fx | results equal bit for bit: %s"
+             % (M, R, (M + chunk - 1) // chunk, chunk, _stats(per["catalogue"]), _stats(per["host"]), b / a, same))
+    emit("== catalogue (ii): bytes per call, derived from the shapes (L = %d, W = %d, n = %d; the catalogue itself, 4 M W bytes, goes up once, "
+         "at set_catalogue)" % (L, W, n))
+    for M, R, chunk, _per, _same in results:
+        emit("M %5d x R %2d | H2D catalogue %6d (R L ids)  host %9d (R M L ids) | D2H catalogue %5d (R (8 n + 4))  host %8d (4 R M)"
+             % (M, R, 4 * R * L, 4 * R * M * L, R * (8 * n + 4), 4 * R * M))
+    emit("   (%d bucket graphs, no others: %s)" % (len(scorer._bucket_graphs), not (scorer._top_graphs or scorer._top_cand_graphs)))
+
+
 RANK_TOPN = 64                                                              # rat_topn_seg's largest page, beside the full ranking
 
 
@@ -1010,6 +1084,7 @@ def main():
     ap.add_argument("--same", action="store_true", help="measure neighbours restricted to equal columns (the chain against the plain scan; score(same=))")
     ap.add_argument("--top", action="store_true", help="measure each request's top-n candidates (rat_topn_seg alone; top_candidates against the host way)")
     ap.add_argument("--rank", action="store_true", help="measure each request's full ranking (rat_rank_seg alone; rank_requests against the host way)")
+    ap.add_argument("--catalogue", action="store_true", help="measure the resident item catalogue (top_catalogue against the host loop over chunks)")
     ap.add_argument("--trace", action="store_true", help="with --delete: only a few deletions per point, for a kernel trace")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -1050,6 +1125,9 @@ def main():
         return
     if args.rank:
         part_rank(emit, args.quick)
+        return
+    if args.catalogue:
+        part_catalogue(emit, args.quick)
         return
     part1(emit, args.quick)
     part2(emit, args.quick)

@@ -192,6 +192,10 @@ _SIGNATURES = {
     "rat_candidates_expand": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, _P, _P]),
     # ... and each request's whole ranking: order, values and every row's place
     "rat_rank_seg": (c_int, [_P, _P, c_int64, _P, _P, _P, _P]),
+    # a device-resident item catalogue: rows built from item indices, exclusion lists, and the running merge of per-chunk pages
+    "rat_catalogue_expand": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int64, c_int, c_int, c_int64, _P, _P]),
+    "rat_topn_exclude": (c_int, [_P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, c_int64, _P, _P]),
+    "rat_topn_merge": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, c_int64, c_int64, c_int64, c_int, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

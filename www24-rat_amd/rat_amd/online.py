@@ -97,6 +97,18 @@ A request can also end with its WHOLE order, for a re-ranker behind the model, r
 bit for bit, ``rank`` every row's place in its request — device tensors of B entries, any request length, nothing read back.  Their
 captured chains live in ``_rank_graphs`` / ``_rank_cand_graphs``; n > 64 on ``top_*`` stays refused.
 
+The candidates can be INDICES into an item catalogue that lives on the device.  ``set_catalogue(items, cols)`` stores [M, W] ids — per
+item the ids of the columns ``cols`` — as int32 on the device.  ``top_items(contexts, items, request_offsets, n)`` and
+``rank_items(contexts, items, request_offsets)`` are ``top_candidates`` / ``rank_candidates`` with ``items`` [C] catalogue indices in
+place of the [C, W] tuples: ``rat_catalogue_expand`` builds the rows, and the rest is ``top_requests`` / ``rank_requests`` over device
+ids — their chains and their captured graphs, shared with direct callers.  ``top_catalogue(contexts, n, chunk=None, exclude=None)``
+scores every one of R users against ALL M items and returns the best n (catalogue indices, predictions, counts): the catalogue is
+swept in passes of ``chunk`` items per user — the sweep form of the expansion, ``score_requests`` with offsets built on the device,
+``rat_topn_seg``, and ``rat_topn_merge`` into a running page per user — with nothing read back between the passes; ``exclude`` =
+(ex_items [E], ex_offsets [R + 1]) names per user the items never to return ("already seen": ``rat_topn_exclude`` before the page,
+a lookup in the merge).  The new kernels run eagerly around the chain; no graph class and no graph dictionary is new.  No ``same=`` /
+``before=`` on these calls either.
+
 Not served online (refused at construction): the config keys ``exact_match_cols`` / ``exact_match_col_indices`` (the restriction is
 per call, ``same=``; not built: ``same`` with ``request_offsets``, and all used columns exact), label-wise retrieval, topK > 32, more
 than 32 retrieval columns, data-parallel models.  Rows are deleted from a
@@ -811,6 +823,7 @@ class OnlineScorer:
         self._rank_cand_graphs = {}    # rank_candidates: (bucket, ..., the candidate columns) -> [eager calls seen, _RankCandGraph | False | None]
         self._cols_dev = {}            # top_candidates / rank_candidates: the candidate columns as a tuple -> the same as an int32 device tensor
         self._found = None             # relabel_where's index list (one entry per row the pool can hold), from its first call on
+        self._catalogue = None         # set_catalogue: (items int32 [M, W] on the device, the columns as an int32 device tensor)
 
     # ------------------------------------------------------------------------------------------------------------------
     def _constants(self, B):
@@ -1246,10 +1259,13 @@ class OnlineScorer:
         if R_given != R:
             raise ValueError("contexts hold %d rows for %d requests (one encoded row per request)" % (R_given, R))
         contexts, candidates = _as_device_ids(contexts, self.device), _as_device_ids(candidates, self.device)
+        return contexts, candidates, cols, self._cols_tensor(cols), off_host, off_dev
+
+    def _cols_tensor(self, cols):
         cols_dev = self._cols_dev.get(cols)
         if cols_dev is None:                                                   # one upload per tuple of columns
             cols_dev = self._cols_dev[cols] = torch.tensor(cols, dtype=torch.int32).to(self.device)
-        return contexts, candidates, cols, cols_dev, off_host, off_dev
+        return cols_dev
 
     def _slab(self, contexts, heads, rows):
         """[rows, L] with the contexts at the rows that open their requests: one indexed copy; no other row is ever read"""
@@ -1373,3 +1389,176 @@ class OnlineScorer:
             else:
                 out = self._rank_cand_eager(self._slab(contexts, self._on_device(heads), P), cand, cols_dev, self._on_device(first_row))
             return self._rank_result(out, C, offsets, scores)
+
+    # ---- a resident item catalogue: candidates as indices, and the best n of all of it ---------------------------------------------
+    def set_catalogue(self, items, cols):
+        """The item catalogue the ``*_items`` / ``top_catalogue`` calls draw candidates from: ``items`` [M, W] integer ids (numpy, host
+        or device tensor) — for each of M items the ids of the columns ``cols`` (W distinct column numbers of the encoded row), what a
+        row of ``top_candidates``' ``candidates`` holds.  Stored as contiguous int32 on the device; replaces any earlier catalogue.
+        Host ids are validated (ValueError before any upload); a device tensor is checked by shape and dtype and converted unread."""
+        cols = _candidate_cols(cols, self.index.row_len)
+        shape = tuple(items.shape) if hasattr(items, "shape") else np.shape(items)
+        if len(shape) != 2:
+            raise ValueError("the catalogue must be [M, W] ids (one row per item), got shape %s" % (shape,))
+        if shape[0] == 0:
+            raise ValueError("empty catalogue")
+        if shape[1] != len(cols):
+            raise ValueError("the catalogue has %d columns for the %d columns in cols" % (shape[1], len(cols)))
+        if torch.is_tensor(items) and items.is_cuda:
+            if items.dtype not in _INT_DTYPES:
+                raise ValueError("the catalogue must hold integers, got dtype %s" % items.dtype)
+            cat = items.detach().to(device=self.device, dtype=torch.int32).contiguous().clone()
+        else:
+            host = items.detach().numpy() if torch.is_tensor(items) else np.asarray(items)
+            if not np.issubdtype(host.dtype, np.integer):
+                raise ValueError("the catalogue must hold integers, got dtype %s" % host.dtype)
+            cat = torch.from_numpy(np.ascontiguousarray(retrieval._as_int32(host, "catalogue"))).to(self.device)
+        self._catalogue = (cat, self._cols_tensor(cols))
+
+    @property
+    def catalogue_size(self):
+        """M, the number of items of the catalogue (0: none set)"""
+        return 0 if self._catalogue is None else self._catalogue[0].shape[0]
+
+    def _catalogue_contexts(self, contexts, what):
+        """-> (the catalogue, its columns on the device, the [R, L] shape of ``contexts``), or ValueError with nothing launched"""
+        if self._catalogue is None:
+            raise ValueError("%s: no catalogue is set (set_catalogue(items, cols))" % what)
+        shape = tuple(contexts.shape) if hasattr(contexts, "shape") else np.shape(contexts)
+        if len(shape) != 2 or shape[0] == 0:
+            raise ValueError("contexts must be [R, L] encoded rows, one per request, got shape %s" % (shape,))
+        if shape[1] != self.index.row_len:
+            raise ValueError("contexts have %d columns, the pool's rows have %d" % (shape[1], self.index.row_len))
+        return self._catalogue + (shape[0],)
+
+    def _item_requests(self, contexts, items, request_offsets, what):
+        """what ``top_items`` takes -> (ids int32 [C, L] on the device, built by ``rat_catalogue_expand``; the offsets as passed on to the
+        request chains), or ValueError with nothing launched"""
+        cat, cols_dev, R_given = self._catalogue_contexts(contexts, what)
+        M = cat.shape[0]
+        shape, dtype = "items must be a 1-D list of catalogue indices", "items must be integers"
+        idx = _device_list(items, shape, dtype, self.device)
+        if idx is None:                                                        # host side: validated
+            host = items.detach().numpy() if torch.is_tensor(items) else np.asarray(items)
+            if host.ndim != 1:
+                raise ValueError("%s, got shape %s" % (shape, tuple(host.shape)))
+            if host.size and not np.issubdtype(host.dtype, np.integer):
+                raise ValueError("%s, got dtype %s" % (dtype, host.dtype))
+            if host.size and (host.min() < 0 or host.max() >= M):
+                raise ValueError("items: index outside [0, %d), the items of the catalogue" % M)
+        C = idx.numel() if idx is not None else host.size
+        if C == 0:
+            raise ValueError("empty request")
+        off_host, off_dev = _request_offsets(request_offsets, C)
+        R = (len(off_host) if off_host is not None else off_dev.numel()) - 1
+        if R_given != R:
+            raise ValueError("contexts hold %d rows for %d requests (one encoded row per request)" % (R_given, R))
+        if idx is None:
+            idx = torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(self.device, non_blocking=True)
+        else:                                                                  # device side: unread; clamped here so that no wide index wraps
+            idx = idx.clamp(0, M - 1).to(torch.int32)
+        contexts = _as_device_ids(contexts, self.device)
+        slab = self._slab(contexts, self._heads(off_host, off_dev, C, False), C)
+        ids = ops.catalogue_expand(slab, cat, cols_dev, _first_rows(off_host, off_dev, C, self.device), items=idx, lib=self._lib)
+        return ids, off_host if off_host is not None else off_dev
+
+    def top_items(self, contexts, items, request_offsets, n, scores=False):
+        """``top_candidates`` with the candidates given as INDICES into the catalogue: ``contexts`` [R, L] encoded rows (their entries in
+        the catalogue's columns are ignored), ``items`` [C] catalogue indices (host: validated, every entry in [0, M); device: used
+        unread, clamped), ``request_offsets`` [R + 1] over them.  C indices go up instead of C W ids.  The rows are built on the device
+        (``rat_catalogue_expand``, after one indexed copy of the contexts) and handed to ``top_requests`` as a pair of device ids and
+        the offsets, so its chain and its captured graphs are shared with direct callers.  Returns what ``top_candidates`` returns,
+        positions counting a request's items from 0."""
+        if self.model.training:
+            raise RuntimeError("OnlineScorer.top_items needs the model in eval mode (model.eval())")
+        n = _top_n(n)
+        with torch.no_grad():
+            return self.top_requests(self._item_requests(contexts, items, request_offsets, "top_items"), n, scores=scores)
+
+    def rank_items(self, contexts, items, request_offsets, scores=False):
+        """``rank_candidates`` with the candidates given as indices into the catalogue (as ``top_items`` takes them), through
+        ``rank_requests``' chain.  Returns what ``rank_candidates`` returns."""
+        if self.model.training:
+            raise RuntimeError("OnlineScorer.rank_items needs the model in eval mode (model.eval())")
+        with torch.no_grad():
+            return self.rank_requests(self._item_requests(contexts, items, request_offsets, "rank_items"), scores=scores)
+
+    def _exclusion(self, exclude, R, M):
+        """what ``top_catalogue`` takes as ``exclude`` -> (ex_items int32 [E], ex_offsets int64 [R + 1]) on the device.  Host lists are
+        validated — integers in [0, M), offsets from 0 to E ascending — and sorted per request; device lists are checked by shape and
+        dtype and used unread (they must be sorted per request)"""
+        if not isinstance(exclude, (tuple, list)) or len(exclude) != 2:
+            raise ValueError("exclude is a pair (ex_items [E], ex_offsets [R + 1])")
+        ex_items, ex_offsets = exclude
+        dev_items = _device_list(ex_items, "ex_items must be a 1-D list of catalogue indices", "ex_items must be integers", self.device)
+        dev_off = _device_list(ex_offsets, "ex_offsets must be a 1-D list of %d offsets (one more than requests)" % (R + 1),
+                               "ex_offsets must be integers", self.device, fits=lambda k: k == R + 1)
+        if (dev_items is None) != (dev_off is None):
+            raise ValueError("exclude: ex_items and ex_offsets sit both on the host or both on the device")
+        if dev_items is not None:
+            return dev_items.clamp(-1, M).to(torch.int32), dev_off
+        items = ex_items.detach().numpy() if torch.is_tensor(ex_items) else np.asarray(ex_items)
+        off = ex_offsets.detach().numpy() if torch.is_tensor(ex_offsets) else np.asarray(ex_offsets)
+        if items.ndim != 1 or (items.size and not np.issubdtype(items.dtype, np.integer)):
+            raise ValueError("ex_items must be a 1-D list of integer catalogue indices, got shape %s, dtype %s" % (tuple(items.shape), items.dtype))
+        if off.ndim != 1 or off.size != R + 1 or not np.issubdtype(off.dtype, np.integer):
+            raise ValueError("ex_offsets must be a 1-D list of %d integer offsets (one more than requests), got shape %s, dtype %s"
+                             % (R + 1, tuple(off.shape), off.dtype))
+        off = off.astype(np.int64)
+        if off[0] != 0 or off[-1] != items.size or (np.diff(off) < 0).any():
+            raise ValueError("ex_offsets must ascend from 0 to the number of excluded items (%d)" % items.size)
+        if items.size and (items.min() < 0 or items.max() >= M):
+            raise ValueError("exclude: index outside [0, %d), the items of the catalogue" % M)
+        items = items.astype(np.int32)
+        ordered = np.concatenate([np.sort(items[a:b]) for a, b in zip(off[:-1], off[1:])] + [np.zeros(0, dtype=np.int32)])
+        return (torch.from_numpy(np.ascontiguousarray(ordered)).to(self.device, non_blocking=True),
+                torch.from_numpy(np.ascontiguousarray(off)).to(self.device, non_blocking=True))
+
+    def top_catalogue(self, contexts, n, chunk=None, exclude=None, scores=False):
+        """The best ``n`` items of the WHOLE catalogue for each of R users: ``contexts`` [R, L] encoded rows -> device tensors (items
+        int32 [R, n], catalogue indices, best first, -1 padded; y fp32 [R, n] their predictions; lens int32 [R]) — per request
+        ``np.argsort(-y_r, kind="stable")[:n]`` over its M predictions, equal predictions by ascending index.  ``scores=True``:
+        additionally the full predictions fp32 [R, M].  The catalogue is swept in passes of ``chunk`` items per request (default
+        ``max(1, graph_max_batch // R)``, at most M; the last pass takes what remains).  Per pass: ``rat_catalogue_expand`` in its sweep
+        form, ``score_requests`` over device ids and device offsets (its chain, its bucket graphs), ``rat_topn_exclude`` (with
+        ``exclude`` only), ``rat_topn_seg``, ``rat_topn_merge`` into the running page — nothing is read back between the passes.
+        ``exclude`` = (ex_items [E], ex_offsets [R + 1]): request r never gets the items ``ex_items[ex_offsets[r]:ex_offsets[r + 1]]``
+        ("what the user has already seen").  On the host the lists are validated and sorted per request (repeats allowed, entries in
+        [0, M)); on the device they are used unread and must be sorted per request.  Excluded items keep their real values in the full
+        predictions.  Limit: with ``exclude``, the result equals the reference order for predictions that are not NaN; an excluded
+        item is never returned, NaN-valued items may be missing from the tail of a page."""
+        if self.model.training:
+            raise RuntimeError("OnlineScorer.top_catalogue needs the model in eval mode (model.eval())")
+        n = _top_n(n)
+        cat, cols_dev, R = self._catalogue_contexts(contexts, "top_catalogue")
+        M = cat.shape[0]
+        if chunk is None:
+            chunk = max(1, self.graph_max_batch // R)
+        elif isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or int(chunk) < 1:
+            raise ValueError("chunk must be an integer >= 1 (items per request per pass), got %r" % (chunk,))
+        chunk = min(int(chunk), M)
+        ex_items = ex_off = None
+        if exclude is not None:
+            ex_items, ex_off = self._exclusion(exclude, R, M)
+        contexts = _as_device_ids(contexts, self.device)
+        with torch.no_grad():
+            run_item = torch.full((R, n), -1, dtype=torch.int32, device=self.device)
+            run_val = torch.zeros((R, n), dtype=torch.float32, device=self.device)
+            run_len = torch.zeros((R,), dtype=torch.int32, device=self.device)
+            full = torch.empty((R, M), dtype=torch.float32, device=self.device) if scores else None
+            requests = torch.arange(R + 1, dtype=torch.int64, device=self.device)
+            plans = {}                                                         # items per request -> (offsets, heads, first_row): two sizes at most
+            for i0 in range(0, M, chunk):
+                m = min(chunk, M - i0)
+                if m not in plans:
+                    off = requests * m
+                    plans[m] = (off, off[:-1].contiguous(), off[:-1, None].expand(R, m).reshape(-1).contiguous())    # (R = 1: the reshape is a view of stride 0)
+                off, heads, first_row = plans[m]
+                ids = ops.catalogue_expand(self._slab(contexts, heads, R * m), cat, cols_dev, first_row, item0=i0, lib=self._lib)
+                y_pred = self.score_requests((ids, off))[0].contiguous()
+                ranked = y_pred if ex_items is None else ops.topn_exclude(y_pred, first_row, i0, m, ex_items, ex_off, lib=self._lib)
+                pos, val, lens = ops.topn_seg(ranked, first_row, n, lib=self._lib)
+                ops.topn_merge(run_item, run_val, run_len, pos, val, lens, heads, i0, ex_items, ex_off, lib=self._lib)
+                if scores:
+                    full[:, i0:i0 + m] = y_pred.view(R, m)
+            return (run_item, run_val, run_len, full) if scores else (run_item, run_val, run_len)

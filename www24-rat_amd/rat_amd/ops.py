@@ -1329,3 +1329,104 @@ def rank_seg(y, first_row, lib=None):
     rank = torch.empty((B,), dtype=torch.int32, device=dev)
     lib.call("rat_rank_seg", _p(y), _p(first_row), B, _p(order), _p(val), _p(rank), _stream(y))
     return order, val, rank
+
+
+# ----------------------------------------------------------------------------- a device-resident item catalogue (rat_amd/online.py)
+def _int_arg(v, what, lo):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < lo:
+        raise ValueError("%s must be an integer >= %d, got %r" % (what, lo, v))
+    return int(v)
+
+
+def _exclusion_arg(ex_items, ex_offsets, R, dev, what):
+    """ex_items int32 [E] and ex_offsets int64 [R + 1] on `dev`, checked by shape, dtype and device; the kernels clamp the offsets"""
+    _chk(ex_items, torch.int32, "ex_items"), _chk(ex_offsets, torch.int64, "ex_offsets")
+    if ex_items.ndim != 1 or tuple(ex_offsets.shape) != (R + 1,):
+        raise ValueError("%s: the exclusion lists are ex_items [E] and ex_offsets [%d] (one more than requests), got shapes %s, %s"
+                         % (what, R + 1, tuple(ex_items.shape), tuple(ex_offsets.shape)))
+    if ex_items.device != dev or ex_offsets.device != dev:
+        raise ValueError("%s: the tensors sit on different devices" % what)
+
+
+def catalogue_expand(ctx, cat, cols, first_row, items=None, item0=0, lib=None):
+    """-> ids int32 [B, L] on the inputs' device: ids[b, cols[w]] = cat[i(b), w] (cat int32 [M, W], the catalogue; cols int32 [W] on
+    the device, distinct and in [0, L)), every other column from ctx[first_row[b]] (ctx int32 [B, L]: the row that opens a request
+    holds its context, no other row is read; first_row int64 [B]).  ``items`` int32 [B]: i(b) = items[b]; ``items=None``, the sweep
+    form: i(b) = item0 + (b - first_row[b]), the k-th row of a request is item item0 + k.  Either way i(b) is clamped to [0, M)
+    (include/rat_hip.h: rat_catalogue_expand)."""
+    lib = lib or get_lib()
+    _chk(ctx, torch.int32, "ctx"), _chk(cat, torch.int32, "cat"), _chk(cols, torch.int32, "cols"), _chk(items, torch.int32, "items")
+    if ctx.ndim != 2 or cat.ndim != 2 or cols.ndim != 1 or ctx.shape[0] < 1 or ctx.shape[1] < 1 or cat.shape[0] < 1 or cols.numel() < 1:
+        raise ValueError("catalogue_expand takes ctx [B, L], cat [M, W] and cols [W], got shapes %s, %s, %s"
+                         % (tuple(ctx.shape), tuple(cat.shape), tuple(cols.shape)))
+    B, L = ctx.shape
+    M, W = cat.shape
+    if cols.numel() != W:
+        raise ValueError("catalogue_expand: cat is %d wide for the %d columns in cols" % (W, cols.numel()))
+    if items is not None and tuple(items.shape) != (B,):
+        raise ValueError("catalogue_expand: items must be [%d] (one catalogue index per row of ctx), got shape %s" % (B, tuple(items.shape)))
+    if isinstance(item0, bool) or not isinstance(item0, (int, np.integer)):
+        raise ValueError("catalogue_expand: item0 must be an integer, got %r" % (item0,))
+    dev = ctx.device
+    if cat.device != dev or cols.device != dev or (items is not None and items.device != dev):
+        raise ValueError("catalogue_expand: the tensors sit on different devices")
+    _first_row_arg(first_row, B, dev, "catalogue_expand")
+    out = torch.empty((B, L), dtype=torch.int32, device=dev)
+    lib.call("rat_catalogue_expand", _p(ctx), _p(cat), _p(items), int(item0), _p(cols), _p(first_row), B, L, W, M, _p(out), _stream(ctx))
+    return out
+
+
+def topn_exclude(y, first_row, item0, rows_per_request, ex_items, ex_offsets, lib=None):
+    """-> y' fp32 [B]: -inf where the catalogue item of row b, item0 + (b - first_row[b]), is in the exclusion list of request
+    first_row[b] // rows_per_request — ex_items int32 [E], ascending inside ex_offsets[r] .. ex_offsets[r + 1] (int64 [R + 1]) —,
+    otherwise y[b] bit for bit (include/rat_hip.h: rat_topn_exclude)."""
+    lib = lib or get_lib()
+    _chk(y, name="y")
+    if y.ndim != 1 or y.numel() < 1:
+        raise ValueError("topn_exclude takes a non-empty 1-D vector y, got shape %s" % (tuple(y.shape),))
+    B, dev = y.numel(), y.device
+    _first_row_arg(first_row, B, dev, "topn_exclude")
+    if isinstance(item0, bool) or not isinstance(item0, (int, np.integer)):
+        raise ValueError("topn_exclude: item0 must be an integer, got %r" % (item0,))
+    m = _int_arg(rows_per_request, "topn_exclude: rows_per_request", 1)
+    if ex_offsets is None or ex_items is None or ex_offsets.ndim != 1 or ex_offsets.numel() < 2:
+        raise ValueError("topn_exclude takes ex_items [E] and ex_offsets [R + 1]")
+    R = ex_offsets.numel() - 1
+    _exclusion_arg(ex_items, ex_offsets, R, dev, "topn_exclude")
+    out = torch.empty_like(y)
+    lib.call("rat_topn_exclude", _p(y), _p(first_row), int(item0), m, _p(ex_items), _p(ex_offsets), ex_items.numel(), R, B, _p(out),
+             _stream(y))
+    return out
+
+
+def topn_merge(run_item, run_val, run_len, pos, val, lens, heads, item0, ex_items=None, ex_offsets=None, lib=None):
+    """Merges a chunk's page into the running page of R requests IN PLACE (nothing is returned): run_item int32 [R, n], run_val fp32
+    [R, n], run_len int32 [R]; the chunk's page is ``topn_seg``'s (pos int32 [B, n], val fp32 [B, n], lens int32 [B]) at the rows
+    heads int64 [R], an entry's catalogue item item0 + pos.  Entries whose item is in the request's exclusion list (ex_items int32
+    [E], ex_offsets int64 [R + 1]; both None: no lists) are dropped; the rest merge in topn_seg's order over (value, item), a running
+    entry before a chunk entry of equal value; the first n survive, padded with -1 / 0.0 (include/rat_hip.h: rat_topn_merge)."""
+    lib = lib or get_lib()
+    _chk(run_item, torch.int32, "run_item"), _chk(run_val, name="run_val"), _chk(run_len, torch.int32, "run_len")
+    _chk(pos, torch.int32, "pos"), _chk(val, name="val"), _chk(lens, torch.int32, "lens"), _chk(heads, torch.int64, "heads")
+    if run_item.ndim != 2 or run_item.shape[0] < 1 or not 1 <= run_item.shape[1] <= MAX_TOPN:
+        raise ValueError("topn_merge takes a running page run_item [R, n] with 1 <= n <= %d, got shape %s" % (MAX_TOPN, tuple(run_item.shape)))
+    R, n = run_item.shape
+    if tuple(run_val.shape) != (R, n) or tuple(run_len.shape) != (R,) or tuple(heads.shape) != (R,):
+        raise ValueError("topn_merge: run_val must be [%d, %d], run_len and heads [%d], got shapes %s, %s, %s"
+                         % (R, n, R, tuple(run_val.shape), tuple(run_len.shape), tuple(heads.shape)))
+    if pos.ndim != 2 or pos.shape[0] < 1 or pos.shape[1] != n or val.shape != pos.shape or tuple(lens.shape) != (pos.shape[0],):
+        raise ValueError("topn_merge: the chunk's page is pos [B, %d], val [B, %d], lens [B], got shapes %s, %s, %s"
+                         % (n, n, tuple(pos.shape), tuple(val.shape), tuple(lens.shape)))
+    if isinstance(item0, bool) or not isinstance(item0, (int, np.integer)):
+        raise ValueError("topn_merge: item0 must be an integer, got %r" % (item0,))
+    dev = run_item.device
+    if any(t.device != dev for t in (run_val, run_len, pos, val, lens, heads)):
+        raise ValueError("topn_merge: the tensors sit on different devices")
+    if (ex_items is None) != (ex_offsets is None):
+        raise ValueError("topn_merge: ex_items and ex_offsets come together")
+    E = 0
+    if ex_items is not None:
+        _exclusion_arg(ex_items, ex_offsets, R, dev, "topn_merge")
+        E = ex_items.numel()
+    lib.call("rat_topn_merge", _p(run_item), _p(run_val), _p(run_len), _p(pos), _p(val), _p(lens), _p(heads), int(item0),
+             _p(ex_items) if E else None, _p(ex_offsets) if E else None, E, R, pos.shape[0], n, _stream(run_item))
