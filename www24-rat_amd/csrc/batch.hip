@@ -11,8 +11,7 @@
 //     y_true[b]      = data_labels[rows[b]]
 // nbr(b, k) = retr_indices[rows[b]][k], a NEGATIVE entry counting from the end of the pool exactly like the numpy fancy
 // index of the reference does (its -1 padding of short neighbour lists therefore selects the last pool row).
-#include "rat_device.h"
-#include "../../include/rat_hip.h"
+#include "pool_common.h"
 
 namespace {
 
@@ -33,15 +32,14 @@ struct BatchArgs {
     int64_t capacity;        // POOL_RING only: slots of the ring
 };
 
-enum { POOL_HOST = 0, POOL_DEV = 1, POOL_RING = 2 };
-
 // one thread per output id: consecutive threads write consecutive ints of idx (coalesced); the source rows are L ints
 // (80 bytes at the north-star config) fetched by L neighbouring lanes
 // DEV: the pool's row count — what a negative neighbour index counts back from — is read from device memory: the pool of an online
 // index with reserved capacity grows under a captured request, and -1 must keep resolving to its last LIVE row
 // POOL_RING: the pool is a ring (a sliding window): a neighbour index is a LOGICAL position (0 = oldest live row; a negative one counts
-// back from the row count first) and lives in slot head + index, minus capacity when that is >= capacity.  Count, head and the
-// logical index are clamped to their domains, so no slot outside the buffers is addressed whatever the header holds.
+// back from the row count first) and lives in slot head + index, wrapped (pool_common.h: the forms, ring_head, ring_wrap).  Count,
+// head and the logical index are clamped to their domains, so no slot outside the buffers is addressed whatever the header holds; the
+// count keeps this kernel's own rule — POOL_RING: [1, capacity] (a negative index counts back from at least one row), POOL_DEV: as read.
 template <int POOL>
 __global__ void __launch_bounds__(256) batch_assemble_kernel(BatchArgs a) {
     const int T = a.K + 1;
@@ -49,8 +47,7 @@ __global__ void __launch_bounds__(256) batch_assemble_kernel(BatchArgs a) {
     [[maybe_unused]] int64_t head = 0;
     if constexpr (POOL == POOL_RING) {
         N = N < 1 ? 1 : (N > a.capacity ? a.capacity : N);
-        head = a.n_dev[1];
-        head = head < 0 ? 0 : (head >= a.capacity ? a.capacity - 1 : head);
+        head = ring_head(a.n_dev, a.capacity);
     }
     const int64_t total = (int64_t)a.B * T * a.L;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
@@ -71,8 +68,7 @@ __global__ void __launch_bounds__(256) batch_assemble_kernel(BatchArgs a) {
             if (nb < 0) nb += N;
             if constexpr (POOL == POOL_RING) {
                 nb = nb < 0 ? 0 : (nb >= N ? N - 1 : nb);
-                nb += head;
-                nb = nb >= a.capacity ? nb - a.capacity : nb;
+                nb = ring_wrap(nb + head, a.capacity);
             }
             v = a.pool_ids[nb * a.L + c];
             if (c == 0) a.label_ids[bt] = (int32_t)a.pool_labels[nb];

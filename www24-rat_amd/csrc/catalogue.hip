@@ -4,8 +4,8 @@
 // cat int32 [M][W], item i's ids of the columns `cols` — and a candidate is an index into them.  Three kernels, on both sides of the
 // unchanged request chain (rat_amd/online.py: top_items, rank_items, top_catalogue):
 //
-//   rat_catalogue_expand    out[b][l] = cat[i(b)][w] where l == cols[w], otherwise ctx[f(b)][l]: rat_candidates_expand with the
-//                           candidate's columns read from the catalogue.  i(b) = items[b] (a list of indices), or — items == NULL,
+//   rat_catalogue_expand    out[b][l] = cat[i(b)][w] where l == cols[w], otherwise ctx[f(b)][l]: rat_candidates_expand (the same kernel,
+//                           order_common.h's expand_kernel) with the candidate's columns read from the catalogue.  i(b) = items[b] (a list of indices), or — items == NULL,
 //                           the SWEEP form — item0 + (b - f(b)): the k-th row of a request is catalogue item item0 + k.
 //   rat_topn_exclude        out_y[b] = -inf where the catalogue item of row b (sweep form) is in its request's exclusion list — an
 //                           ascending int32 list per request, searched by lower bound —, otherwise y[b], the same bits.
@@ -13,7 +13,7 @@
 //                           into the running page of every request, in place: rat_topn_seg's total order over (value, catalogue
 //                           index).  A sweep visits the items in ascending order, so a running entry comes before a chunk entry of
 //                           equal value; inside each page the entries already stand in that order.  Every entry gets
-//                               order_key(value) (topn.hip's: NaN lowest, -0.0 == +0.0) + 1, 0 for an empty slot
+//                               order_key(value) (order_common.h's, as rat_topn_seg ranked by it: NaN lowest, -0.0 == +0.0) + 1, 0 for an empty slot
 //                           and its place is the number of entries that come before it: 2 x 64 comparisons per lane out of LDS, ONE
 //                           wave per request.  Chunk entries whose item is excluded are dropped first (looked up, not judged by value).
 //                           Values are moved, never computed with.
@@ -23,25 +23,12 @@
 // anything, item0 is clamped to [-2^31, 2^32] (which changes no clamped item: |b - f(b)| < 2^31) so that no sum overflows, and the places
 // of a merge are a permutation of 0 .. entries - 1 whatever the pages hold (ties fall to the page, then to the slot).
 // No atomics, no communication between work-groups, nothing allocated or read back; every output element is written by every launch.
-#include "rat_device.h"
-#include "../../include/rat_hip.h"
+#include "order_common.h"
 
 namespace {
 
-constexpr int CT_MAX_L = 8192;             // the inverse column map is L words of LDS (rat_candidates_expand's limit)
 constexpr int CT_WAVE = 64;                // rat_topn_merge: one wave per request, RAT_MAX_TOPN slots per page
 static_assert(RAT_MAX_TOPN <= CT_WAVE, "a lane holds one slot of each page");
-
-__device__ __forceinline__ int64_t clamp_to(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int64_t clamp_row(int64_t r, int64_t B) { return clamp_to(r, 0, B - 1); }
-
-// topn.hip's order_key: fp32 -> uint32, ascending with the value, NaN -> 0, -0.0 -> the key of +0.0; the largest is +inf's, 0xFF800000
-__device__ __forceinline__ uint32_t order_key(float v) {
-    uint32_t u = rat_fbits(v);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // is `item` in list[lo, hi)?  The list is ascending: lower bound, then one comparison.  lo <= hi inside the list, so every probe is;
 // an unsorted list gives a wrong answer, never a wrong address
@@ -72,43 +59,11 @@ struct CatExpandArgs {
     int32_t* out;                // [B][L]
     int64_t item0, B, M;
     int L, W;
+    // expand_kernel's (order_common.h) source of a candidate's own columns: the catalogue row of item i(b)
+    __device__ const int32_t* row(int64_t b, int64_t h) const {
+        return cat + clamp_to(items != nullptr ? (int64_t)items[b] : item0 + (b - h), 0, M - 1) * W;
+    }
 };
-
-// candidates_expand_kernel (topn.hip) with the candidate's row taken from the catalogue: work item = one word (VEC: one 16-byte group
-// of four) of out, inv[l] = the w with cols[w] == l, or -1, built by every work-group
-template <bool VEC>
-__global__ void __launch_bounds__(256) catalogue_expand_kernel(CatExpandArgs a) {
-    RAT_DYN_SMEM(smem);
-    int32_t* inv = reinterpret_cast<int32_t*>(smem);
-    for (int l = threadIdx.x; l < a.L; l += 256) inv[l] = -1;
-    __syncthreads();
-    for (int w = threadIdx.x; w < a.W; w += 256) {
-        const int32_t c = a.cols[w];
-        if (c >= 0 && c < a.L) inv[c] = w;                                      // a column outside the row is skipped
-    }
-    __syncthreads();
-    const int per_row = VEC ? a.L / 4 : a.L;
-    const int64_t total = a.B * per_row;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int64_t b = e / per_row;
-        const int l = (int)(e % per_row) * (VEC ? 4 : 1);
-        const int64_t h = clamp_row(a.first_row[b], a.B);
-        const int64_t i = clamp_to(a.items != nullptr ? (int64_t)a.items[b] : a.item0 + (b - h), 0, a.M - 1);
-        const int32_t* c = a.cat + i * a.W;
-        if (VEC) {
-            rat_u4 v = *reinterpret_cast<const rat_u4*>(a.ctx + h * a.L + l);
-            const int w0 = inv[l], w1 = inv[l + 1], w2 = inv[l + 2], w3 = inv[l + 3];
-            if (w0 >= 0) v.x = (unsigned)c[w0];
-            if (w1 >= 0) v.y = (unsigned)c[w1];
-            if (w2 >= 0) v.z = (unsigned)c[w2];
-            if (w3 >= 0) v.w = (unsigned)c[w3];
-            *reinterpret_cast<rat_u4*>(a.out + b * a.L + l) = v;
-        } else {
-            const int w = inv[l];
-            a.out[b * a.L + l] = w >= 0 ? c[w] : a.ctx[h * a.L + l];
-        }
-    }
-}
 
 struct ExcludeArgs {
     const float* y;              // [B]
@@ -195,7 +150,6 @@ __global__ void __launch_bounds__(CT_WAVE) topn_merge_kernel(MergeArgs a) {
     if (t == 0) a.run_len[r] = cnt;
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // |b - f(b)| < 2^31 and a position is an int32: behind this clamp no item0 + k overflows, and no item clamped to [0, M) changes
 int64_t item0_arg(int64_t item0) { return item0 < -0x80000000LL ? -0x80000000LL : (item0 > 0x100000000LL ? 0x100000000LL : item0); }
 
@@ -205,18 +159,11 @@ extern "C" int rat_catalogue_expand(const int32_t* ctx, const int32_t* cat, cons
                                     const int64_t* first_row, int64_t B, int L, int W, int64_t M, int32_t* out, void* stream) {
     RAT_REQUIRE(ctx && cat && cols && first_row && out, "null pointer");
     RAT_REQUIRE(B >= 1 && B <= 0x7fffffffLL, "B must be in [1, 2^31 - 1]");
-    RAT_REQUIRE(L >= 1 && L <= CT_MAX_L, "L must be in [1, 8192]");
-    RAT_REQUIRE(W >= 1 && W <= CT_MAX_L, "W must be in [1, 8192]");
+    RAT_REQUIRE(L >= 1 && L <= EXPAND_MAX_L, "L must be in [1, 8192]");
+    RAT_REQUIRE(W >= 1 && W <= EXPAND_MAX_L, "W must be in [1, 8192]");
     RAT_REQUIRE(M >= 1 && M <= 0x7fffffffLL, "M must be in [1, 2^31 - 1]");
     CatExpandArgs a{ctx, cat, items, cols, first_row, out, item0_arg(item0), B, M, L, W};
-    const bool vec = L % 4 == 0 && al16(ctx) && al16(out);
-    const int64_t blocks = (B * (vec ? L / 4 : L) + 255) / 256;
-    const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
-    const size_t lds = (size_t)L * sizeof(int32_t);
-    if (vec)
-        RAT_LAUNCH(catalogue_expand_kernel<true>, grid, 256, lds, stream, a);
-    else
-        RAT_LAUNCH(catalogue_expand_kernel<false>, grid, 256, lds, stream, a);
+    expand_launch(a, stream);
     return rat_check_launch("rat_catalogue_expand");
 }
 

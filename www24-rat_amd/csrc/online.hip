@@ -16,8 +16,8 @@
 // Both scan-side merges are per WAVE (lanes exchange their list heads through a wave-private LDS tile, no work-group barrier);
 // the four waves' lists of a work-group are then ranked against each other after the one barrier of the kernel.
 // Nothing here allocates, synchronises or uses a floating-point atomic: the pair is captured into the serving graph (rat_amd/online.py).
-#include "rat_device.h"
-#include "../../include/rat_hip.h"
+#include "bm25_scan.h"
+#include "pool_common.h"
 
 namespace {
 
@@ -34,17 +34,6 @@ constexpr int64_t ON_SINGLE_TILES = 256;
 constexpr int64_t ON_TARGET_GROUPS = 512;
 constexpr int64_t ON_MIN_RANGE_ROWS = 1024;
 constexpr int64_t ON_AUTO_MAX_SPLITS = 256;
-
-__device__ __forceinline__ bool better(double sa, int64_t ia, double sb, int64_t ib) {   // (score desc, index asc)
-    return sa > sb || (sa == sb && ia < ib);
-}
-// candidate (so, io) against the running best (cs, ci); an index < 0 is "no entry"
-__device__ __forceinline__ void take_better(double so, int64_t io, double& cs, int64_t& ci) {
-    if (io >= 0 && (ci < 0 || better(so, io, cs, ci))) {
-        cs = so;
-        ci = io;
-    }
-}
 
 // ---- arg-max over the 64 lanes of ONE wave, QT independent problems at once: every lane passes a candidate per problem and gets
 // the wave's best back.  Two levels through a wave-private LDS tile (64 heads -> 8 group bests -> 1), double-buffered by the
@@ -117,7 +106,7 @@ struct SplitArgs {
 // LOGICAL row n (0 = oldest) lives in slot head + n, minus stride when that is >= stride (head + n < 2 stride, so a compare and a
 // subtract).  Only the address of the one id load is physical: ranges, list entries, ties and the merge all see logical rows.
 // Everything after the prologue is the same code, so the same fp64 sums in the same order and the same merge.
-enum { POOL_HOST = 0, POOL_DEV = 1, POOL_RING = 2 };
+// (The forms, their header clamps and the ring's wrap are pool_common.h's.)
 
 // HORIZON (rat_bm25_topk_split_before): query q's candidates are the logical rows below before[q], clamped to [0, N] on the device.
 // The rows are scored as ever and a row at or past its query's horizon then scores 0 — one compare and select per (row, query) after
@@ -139,6 +128,9 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
     __shared__ int64_t wl_i[ON_WAVES][QT][KMAX];
     const int tid = threadIdx.x, lane = rat_lane(), wave = rat_wave();
     const int64_t ntiles = (a.Q + QT - 1) / QT;
+    // the prologue keeps its own clamps (pool_view's, spelled out): through pool_view the same values compile to another
+    // instruction stream in 12 of this kernel's 18 instantiations (profiles/online/shared_code_resource_usage.txt), and the scan is
+    // to stay the parent's code
     int64_t N = a.N, stride = a.N;
     [[maybe_unused]] int64_t head = 0;
     if constexpr (POOL != POOL_HOST) {
@@ -176,17 +168,9 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
         }
         double val[QT][KMAX], kth[QT];                     // kth = score of the current K-th entry (0 while the list is not full)
         int64_t idx[QT][KMAX];
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            kth[t] = 0.0;
-#pragma unroll
-            for (int k = 0; k < KMAX; ++k) {
-                val[t][k] = 0.0;
-                idx[t][k] = -1;
-            }
-        }
-        // ---- scan rows [lo, hi) the way bm25_topk_kernel scans [0, N): every lane walks its rows in increasing order, so among
-        //      equal scores the lower index arrives first and a later row must be STRICTLY better than the K-th entry to get in
+        list_init<KMAX, QT>(val, idx, kth);
+        // ---- scan rows [lo, hi) the way bm25_topk_kernel scans [0, N): every lane walks its rows in increasing order and offers
+        //      them to its lists (bm25_scan.h: RAT_BM25_LIST_INSERT, the same text)
         for (int64_t n0 = lo + tid; n0 < hi; n0 += (int64_t)ON_THREADS * RU) {
             double s[RU][QT];
 #pragma unroll
@@ -200,10 +184,7 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
                 for (int u = 0; u < RU; ++u) {                                            // RU independent loads in flight per field
                     const int64_t n = n0 + (int64_t)u * ON_THREADS;
                     int64_t slot = n;
-                    if constexpr (POOL == POOL_RING) {                                    // logical row -> its slot of the ring
-                        slot = n + head;
-                        slot = slot >= stride ? slot - stride : slot;
-                    }
+                    if constexpr (POOL == POOL_RING) slot = ring_wrap(n + head, stride);  // logical row -> its slot of the ring
                     id[u] = n < hi ? a.db_t[(int64_t)f * stride + slot] : -1;
                 }
 #pragma unroll
@@ -240,24 +221,7 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
                 const int64_t n = n0 + (int64_t)u * ON_THREADS;
 #pragma unroll
                 for (int t = 0; t < QT; ++t) {
-                    if (s[u][t] > kth[t]) {                                               // positive AND strictly better than the K-th
-                        double cs = s[u][t];
-                        int64_t ci = n;
-                        bool placed = false;          // once the newcomer sits the rest only shifts down (see bm25_topk_kernel)
-#pragma unroll
-                        for (int k = 0; k < KMAX; ++k) {
-                            if (k < a.K && (placed || cs > val[t][k])) {
-                                placed = true;
-                                const double ts = val[t][k];
-                                const int64_t ti = idx[t][k];
-                                val[t][k] = cs;
-                                idx[t][k] = ci;
-                                cs = ts;
-                                ci = ti;
-                            }
-                            if (k == a.K - 1) kth[t] = val[t][k];
-                        }
-                    }
+                    RAT_BM25_LIST_INSERT(KMAX, val[t], idx[t], kth[t], a.K, s[u][t], n);
                 }
             }
         }
@@ -280,15 +244,7 @@ __global__ void __launch_bounds__(ON_THREADS) bm25_scan_split_kernel(SplitArgs a
 #pragma unroll
                 for (int t = 0; t < QT; ++t) {
                     any |= hx[t] >= 0;
-                    if (hx[t] >= 0 && idx[t][0] == hx[t]) {                                // the winner pops its head
-#pragma unroll
-                        for (int j = 0; j + 1 < KMAX; ++j) {
-                            val[t][j] = val[t][j + 1];
-                            idx[t][j] = idx[t][j + 1];
-                        }
-                        val[t][KMAX - 1] = 0.0;
-                        idx[t][KMAX - 1] = -1;
-                    }
+                    if (hx[t] >= 0 && idx[t][0] == hx[t]) list_pop<KMAX>(val[t], idx[t]);     // the winner pops its head
                     if (lane == t * KMAX + k_end) {
                         wl_v[wave][t][k_end] = hx[t] >= 0 ? hs[t] : 0.0;
                         wl_i[wave][t][k_end] = hx[t];
@@ -666,9 +622,6 @@ __device__ __forceinline__ RingHeader ring_header(const int64_t* header, int64_t
     h.ok = h.n >= 0 && h.n <= capacity && h.head >= 0 && h.head < capacity;
     return h;
 }
-__device__ __forceinline__ int64_t ring_wrap(int64_t slot, int64_t capacity) {     // slot < 2 capacity
-    return slot >= capacity ? slot - capacity : slot;
-}
 
 // pool_append_kernel's work items, every destination through the ring: row i of the batch goes to slot base + i (wrapped) with
 // base = head + n (wrapped) — the slot behind the newest row, which is the oldest row's once the window is full.  64 consecutive lanes
@@ -762,18 +715,17 @@ struct DeleteArgs {
 enum { PLANE_DB_T = 0, PLANE_IDS = 1, PLANE_LABELS = 2 };
 constexpr int64_t DEL_ITEMS_PER_THREAD = 4;            // the grid is sized for this many words per thread at the full capacity
 
-// What both launches of a plane see.  n is clamped to [0, capacity], head to [0, capacity) and del[0] to [0, n], as the ring scan
-// clamps its header: compact positions are [first, n - n_del) and a source is j' + k <= n - n_del - 1 + n_del, a live row whatever
+// What both launches of a plane see.  n is clamped to [0, capacity], head to [0, capacity) (pool_view) and del[0] to [0, n]:
+// compact positions are [first, n - n_del) and a source is j' + k <= n - n_del - 1 + n_del, a live row whatever
 // the list holds — nothing outside the buffers is addressed for any header or list content.
 struct DeleteView {
     int64_t n, head, first, count;                     // count = survivors of the suffix = compact positions to move
 };
 __device__ __forceinline__ DeleteView delete_view(const DeleteArgs& a) {
+    const PoolView pool = pool_view<POOL_RING>(a.header, 0, a.capacity);
     DeleteView v;
-    v.n = a.header[0];
-    v.n = v.n < 0 ? 0 : (v.n > a.capacity ? a.capacity : v.n);
-    v.head = a.header[1];
-    v.head = v.head < 0 ? 0 : (v.head >= a.capacity ? a.capacity - 1 : v.head);
+    v.n = pool.n;
+    v.head = pool.head;
     v.first = a.del[0];
     v.first = v.first < 0 ? 0 : (v.first > v.n ? v.n : v.first);
     v.count = v.n - a.n_del - v.first;
@@ -907,22 +859,6 @@ struct FindArgs {
     int64_t max_out;
     int64_t* ws;             // [groups] counts, [groups] exclusive offsets, [1] total
 };
-
-// the live rows as every launch sees them: n clamped to [0, capacity] and head to [0, capacity), as the ring scan clamps its header
-struct PoolView {
-    int64_t n, head;
-};
-template <int POOL>
-__device__ __forceinline__ PoolView pool_view(const int64_t* header, int64_t n_host, int64_t capacity) {
-    PoolView v{n_host, 0};
-    if constexpr (POOL != POOL_HOST) v.n = header[0];
-    v.n = v.n < 0 ? 0 : (v.n > capacity ? capacity : v.n);
-    if constexpr (POOL == POOL_RING) {
-        v.head = header[1];
-        v.head = v.head < 0 ? 0 : (v.head >= capacity ? capacity - 1 : v.head);
-    }
-    return v;
-}
 
 __device__ __forceinline__ int64_t find_col_offset(const FindArgs& a, int c) {     // wave-uniform: scalar loads
     int64_t col = a.cols[c];
@@ -1066,10 +1002,8 @@ extern "C" int rat_pool_find(const int32_t* store, int64_t row_stride, int64_t c
                              const int32_t* keys, int64_t n_keys, int64_t* out_idx, int64_t max_out, int64_t* out_count, void* workspace,
                              size_t workspace_bytes, int groups, void* stream) {
     RAT_REQUIRE(store && cols && keys && out_count && workspace, "null pointer");
-    RAT_REQUIRE(pool_form == POOL_HOST || pool_form == POOL_DEV || pool_form == POOL_RING, "pool_form must be 0, 1 or 2");
-    RAT_REQUIRE(pool_form == POOL_HOST || header_dev, "null header");
-    RAT_REQUIRE(capacity > 0 && row_stride > 0 && col_stride > 0 && store_cols > 0 && n_keys > 0 && max_out >= 0, "bad dims");
-    RAT_REQUIRE(pool_form != POOL_HOST || (n_rows >= 0 && n_rows <= capacity), "n_rows outside [0, capacity]");
+    RAT_POOL_FORM_CHECK(pool_form, header_dev, n_rows, capacity,
+                        capacity > 0 && row_stride > 0 && col_stride > 0 && store_cols > 0 && n_keys > 0 && max_out >= 0);
     RAT_REQUIRE(n_cols > 0 && n_cols <= FIND_MAX_COLS, "1 to 32 key columns are supported");
     RAT_REQUIRE(max_out == 0 || out_idx, "null out_idx");
     RAT_REQUIRE(groups >= 0 && groups <= FIND_MAX_GROUPS, "groups must be 0 (library's choice) or 1..4096");
@@ -1082,30 +1016,20 @@ extern "C" int rat_pool_find(const int32_t* store, int64_t row_stride, int64_t c
     RAT_REQUIRE(((uintptr_t)workspace & 7) == 0, "workspace must be 8-byte aligned");
     FindArgs a{store, row_stride, col_stride, header_dev, n_rows, capacity, cols, keys, n_keys, n_cols, store_cols, groups,
                out_idx, out_count, max_out, static_cast<int64_t*>(workspace)};
-    if (pool_form == POOL_HOST) return launch_find<POOL_HOST>(a, stream);
-    if (pool_form == POOL_DEV) return launch_find<POOL_DEV>(a, stream);
-    return launch_find<POOL_RING>(a, stream);
+    return dispatch_pool(pool_form, [&](auto form) { return launch_find<decltype(form)::value>(a, stream); });
 }
 
 extern "C" int rat_pool_set_labels(float* pool_labels, int pool_form, const int64_t* header_dev, int64_t n_rows, int64_t capacity,
                                    const int64_t* indices, const float* labels, int64_t m, int label_stride, void* stream) {
     RAT_REQUIRE(pool_labels, "null pointer");
-    RAT_REQUIRE(pool_form == POOL_HOST || pool_form == POOL_DEV || pool_form == POOL_RING, "pool_form must be 0, 1 or 2");
-    RAT_REQUIRE(pool_form == POOL_HOST || header_dev, "null header");
-    RAT_REQUIRE(capacity > 0, "bad dims");
-    RAT_REQUIRE(pool_form != POOL_HOST || (n_rows >= 0 && n_rows <= capacity), "n_rows outside [0, capacity]");
+    RAT_POOL_FORM_CHECK(pool_form, header_dev, n_rows, capacity, capacity > 0);
     RAT_REQUIRE(label_stride == 0 || label_stride == 1, "label_stride must be 1 (a label per index) or 0 (one label for all)");
     if (m <= 0) return 0;                              // nothing to write: nothing is launched
     RAT_REQUIRE(indices && labels, "null pointer");
     SetLabelsArgs a{pool_labels, header_dev, indices, labels, n_rows, capacity, m, label_stride};
     const int64_t blocks = (m + 255) / 256;
     const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
-    if (pool_form == POOL_HOST)
-        RAT_LAUNCH(pool_set_labels_kernel<POOL_HOST>, grid, 256, 0, stream, a);
-    else if (pool_form == POOL_DEV)
-        RAT_LAUNCH(pool_set_labels_kernel<POOL_DEV>, grid, 256, 0, stream, a);
-    else
-        RAT_LAUNCH(pool_set_labels_kernel<POOL_RING>, grid, 256, 0, stream, a);
+    dispatch_pool(pool_form, [&](auto form) { RAT_LAUNCH(pool_set_labels_kernel<decltype(form)::value>, grid, 256, 0, stream, a); });
     return rat_check_launch("rat_pool_set_labels");
 }
 
@@ -1153,21 +1077,13 @@ extern "C" int rat_pool_gather_rows(const int32_t* pool_ids, const float* pool_l
                                     int64_t n_rows, int64_t capacity, const int64_t* indices, int32_t* out_ids, float* out_labels,
                                     int64_t* out_before, int64_t n_indices, int row_len, void* stream) {
     RAT_REQUIRE(pool_ids && pool_labels, "null pointer");
-    RAT_REQUIRE(pool_form == POOL_HOST || pool_form == POOL_DEV || pool_form == POOL_RING, "pool_form must be 0, 1 or 2");
-    RAT_REQUIRE(pool_form == POOL_HOST || header_dev, "null header");
-    RAT_REQUIRE(capacity > 0 && row_len > 0, "bad dims");
-    RAT_REQUIRE(pool_form != POOL_HOST || (n_rows >= 0 && n_rows <= capacity), "n_rows outside [0, capacity]");
+    RAT_POOL_FORM_CHECK(pool_form, header_dev, n_rows, capacity, capacity > 0 && row_len > 0);
     if (n_indices <= 0) return 0;                      // nothing to gather: nothing is launched
     RAT_REQUIRE(indices && out_ids && out_labels && out_before, "null pointer");
     GatherRowsArgs a{pool_ids, pool_labels, header_dev, indices, out_ids, out_labels, out_before, n_rows, capacity, n_indices, row_len};
     const int64_t blocks = (n_indices * row_len + 255) / 256;
     const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
-    if (pool_form == POOL_HOST)
-        RAT_LAUNCH(pool_gather_rows_kernel<POOL_HOST>, grid, 256, 0, stream, a);
-    else if (pool_form == POOL_DEV)
-        RAT_LAUNCH(pool_gather_rows_kernel<POOL_DEV>, grid, 256, 0, stream, a);
-    else
-        RAT_LAUNCH(pool_gather_rows_kernel<POOL_RING>, grid, 256, 0, stream, a);
+    dispatch_pool(pool_form, [&](auto form) { RAT_LAUNCH(pool_gather_rows_kernel<decltype(form)::value>, grid, 256, 0, stream, a); });
     return rat_check_launch("rat_pool_gather_rows");
 }
 
@@ -1176,24 +1092,19 @@ extern "C" int rat_bm25_topk_split_before(const int32_t* db_ids_field_major, int
                                           double* out_values, int64_t* out_indices, int64_t* out_lens, void* workspace,
                                           size_t workspace_bytes, int64_t n_qry, int n_fields, int topk, int splits, void* stream) {
     RAT_REQUIRE(db_ids_field_major && qry_ids && qry_idf && before_dev && out_values && out_indices && out_lens, "null pointer");
-    RAT_REQUIRE(pool_form == POOL_HOST || pool_form == POOL_DEV || pool_form == POOL_RING, "pool_form must be 0, 1 or 2");
-    RAT_REQUIRE(pool_form == POOL_HOST || header_dev, "null header");
-    RAT_REQUIRE(capacity > 0 && n_qry > 0 && n_fields > 0 && topk > 0, "bad dims");
-    RAT_REQUIRE(pool_form != POOL_HOST || (n_rows >= 0 && n_rows <= capacity), "n_rows outside [0, capacity]");
+    RAT_POOL_FORM_CHECK(pool_form, header_dev, n_rows, capacity, capacity > 0 && n_qry > 0 && n_fields > 0 && topk > 0);
     RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
     RAT_REQUIRE(topk <= ON_KMAX, "topK > 32 is not supported");
     RAT_REQUIRE(splits >= 0 && splits <= ON_MAX_SPLITS, "splits must be 0 (library's choice) or 1..4096");
     // from the capacity in every form, as rat_bm25_topk_split_dev: one range too goes through the split kernel, which has the horizon
     if (splits == 0) splits = (int)auto_splits(n_qry, capacity, topk);
-    const char* who = "rat_bm25_topk_split_before";
-    if (pool_form == POOL_HOST)
-        return launch_split<POOL_HOST, true>(who, db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
-                                             workspace_bytes, n_rows, nullptr, capacity, n_qry, n_fields, topk, splits, stream, before_dev);
-    if (pool_form == POOL_DEV)
-        return launch_split<POOL_DEV, true>(who, db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
-                                            workspace_bytes, 0, header_dev, capacity, n_qry, n_fields, topk, splits, stream, before_dev);
-    return launch_split<POOL_RING, true>(who, db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
-                                         workspace_bytes, 0, header_dev, capacity, n_qry, n_fields, topk, splits, stream, before_dev);
+    // POOL_HOST: the row count by value and no header; otherwise the header and no count
+    return dispatch_pool(pool_form, [&](auto form) {
+        constexpr int POOL = decltype(form)::value;
+        return launch_split<POOL, true>("rat_bm25_topk_split_before", db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens,
+                                        workspace, workspace_bytes, POOL == POOL_HOST ? n_rows : 0, POOL == POOL_HOST ? nullptr : header_dev,
+                                        capacity, n_qry, n_fields, topk, splits, stream, before_dev);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------ neighbours equal on given columns
@@ -1357,10 +1268,7 @@ extern "C" int rat_bm25_exact_count(const int32_t* db_ids_field_major, int pool_
                                     const int64_t* before_dev, int64_t* out_counts, void* workspace, size_t workspace_bytes,
                                     int64_t n_qry, int row_stride, int n_fields, int groups, void* stream) {
     RAT_REQUIRE(db_ids_field_major && ids && cols && out_counts && workspace, "null pointer");
-    RAT_REQUIRE(pool_form == POOL_HOST || pool_form == POOL_DEV || pool_form == POOL_RING, "pool_form must be 0, 1 or 2");
-    RAT_REQUIRE(pool_form == POOL_HOST || header_dev, "null header");
-    RAT_REQUIRE(capacity > 0 && n_qry > 0 && n_fields > 0 && row_stride > 0, "bad dims");
-    RAT_REQUIRE(pool_form != POOL_HOST || (n_rows >= 0 && n_rows <= capacity), "n_rows outside [0, capacity]");
+    RAT_POOL_FORM_CHECK(pool_form, header_dev, n_rows, capacity, capacity > 0 && n_qry > 0 && n_fields > 0 && row_stride > 0);
     RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
     RAT_REQUIRE(exact_mask_ok(exact_mask, n_fields), "exact_mask must name at least one used column and leave at least one to score");
     RAT_REQUIRE(groups >= 0 && groups <= EC_MAX_GROUPS, "groups must be 0 (library's choice) or 1..4096");
@@ -1372,12 +1280,7 @@ extern "C" int rat_bm25_exact_count(const int32_t* db_ids_field_major, int pool_
                      capacity, n_qry, row_stride, n_fields, groups, exact_mask};
     const int64_t items = (n_qry + EC_QT - 1) / EC_QT * groups;
     const unsigned grid = (unsigned)(items < 65536 ? items : 65536);
-    if (pool_form == POOL_HOST)
-        RAT_LAUNCH(bm25_exact_count_kernel<POOL_HOST>, grid, EC_THREADS, 0, stream, a);
-    else if (pool_form == POOL_DEV)
-        RAT_LAUNCH(bm25_exact_count_kernel<POOL_DEV>, grid, EC_THREADS, 0, stream, a);
-    else
-        RAT_LAUNCH(bm25_exact_count_kernel<POOL_RING>, grid, EC_THREADS, 0, stream, a);
+    dispatch_pool(pool_form, [&](auto form) { RAT_LAUNCH(bm25_exact_count_kernel<decltype(form)::value>, grid, EC_THREADS, 0, stream, a); });
     if (rat_check_launch("rat_bm25_exact_count") != 0) return -1;
     const int64_t blocks = (n_qry + 255) / 256;
     RAT_LAUNCH(bm25_exact_sum_kernel, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream, a.ws, out_counts, n_qry, groups);
@@ -1398,25 +1301,17 @@ extern "C" int rat_bm25_topk_split_exact(const int32_t* db_ids_field_major, int 
                                          int64_t* out_indices, int64_t* out_lens, void* workspace, size_t workspace_bytes,
                                          int64_t n_qry, int n_fields, int topk, int splits, void* stream) {
     RAT_REQUIRE(db_ids_field_major && qry_ids && qry_idf && listing_dev && out_values && out_indices && out_lens, "null pointer");
-    RAT_REQUIRE(pool_form == POOL_HOST || pool_form == POOL_DEV || pool_form == POOL_RING, "pool_form must be 0, 1 or 2");
-    RAT_REQUIRE(pool_form == POOL_HOST || header_dev, "null header");
-    RAT_REQUIRE(capacity > 0 && n_qry > 0 && n_fields > 0 && topk > 0, "bad dims");
-    RAT_REQUIRE(pool_form != POOL_HOST || (n_rows >= 0 && n_rows <= capacity), "n_rows outside [0, capacity]");
+    RAT_POOL_FORM_CHECK(pool_form, header_dev, n_rows, capacity, capacity > 0 && n_qry > 0 && n_fields > 0 && topk > 0);
     RAT_REQUIRE(n_fields <= ON_FMAX, "more than 32 retrieval columns are not supported");
     RAT_REQUIRE(topk <= ON_KMAX, "topK > 32 is not supported");
     RAT_REQUIRE(exact_mask_ok(exact_mask, n_fields), "exact_mask must name at least one used column and leave at least one to score");
     RAT_REQUIRE(splits >= 0 && splits <= ON_MAX_SPLITS, "splits must be 0 (library's choice) or 1..4096");
     if (splits == 0) splits = (int)auto_splits(n_qry, capacity, topk);        // from the capacity, as rat_bm25_topk_split_before
-    const char* who = "rat_bm25_topk_split_exact";
-    if (pool_form == POOL_HOST)
-        return launch_split<POOL_HOST, true, true>(who, db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
-                                                   workspace_bytes, n_rows, nullptr, capacity, n_qry, n_fields, topk, splits, stream,
-                                                   before_dev, exact_mask, listing_dev);
-    if (pool_form == POOL_DEV)
-        return launch_split<POOL_DEV, true, true>(who, db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
-                                                  workspace_bytes, 0, header_dev, capacity, n_qry, n_fields, topk, splits, stream,
-                                                  before_dev, exact_mask, listing_dev);
-    return launch_split<POOL_RING, true, true>(who, db_ids_field_major, qry_ids, qry_idf, out_values, out_indices, out_lens, workspace,
-                                               workspace_bytes, 0, header_dev, capacity, n_qry, n_fields, topk, splits, stream,
-                                               before_dev, exact_mask, listing_dev);
+    return dispatch_pool(pool_form, [&](auto form) {                          // the count or the header, as rat_bm25_topk_split_before
+        constexpr int POOL = decltype(form)::value;
+        return launch_split<POOL, true, true>("rat_bm25_topk_split_exact", db_ids_field_major, qry_ids, qry_idf, out_values, out_indices,
+                                              out_lens, workspace, workspace_bytes, POOL == POOL_HOST ? n_rows : 0,
+                                              POOL == POOL_HOST ? nullptr : header_dev, capacity, n_qry, n_fields, topk, splits, stream,
+                                              before_dev, exact_mask, listing_dev);
+    });
 }

@@ -8,7 +8,7 @@
 //                           place: rank by COUNTING.  One thread per row; the row's rank is the number of rows of its segment that come
 //                           before it in topn.hip's total order — a before b iff y[a] > y[b], or neither compares greater and a < b:
 //                           the rows with a larger 64-bit key
-//                               (order-preserving uint32 of y, NaN -> 0, -0.0 -> +0.0's) << 32  |  0xFFFFFFFF - row
+//                               (order_common.h's order_key of y, NaN -> 0, -0.0 -> +0.0's) << 32  |  0xFFFFFFFF - row
 //                           — and the thread scatters its position and its value to that place.  No floating-point arithmetic touches
 //                           y: out_val carries y's bits.
 //
@@ -25,8 +25,7 @@
 // stops at the first tile boundary at or behind that end, which every thread reads off first_row itself — no vote per tile.  A long
 // segment is thereby spread over all the work-groups that hold its rows, with no communication between them, at O(segment length) LDS
 // reads per row.  No atomics, nothing allocated or read back, one launch: captured into the serving graph.
-#include "rat_device.h"
-#include "../../include/rat_hip.h"
+#include "order_common.h"
 
 namespace {
 
@@ -35,16 +34,6 @@ constexpr int RK_WAVES = RK_THREADS / 64;
 constexpr int RK_TILE = 1024;              // rows whose (key, f) one LDS tile holds
 constexpr int RK_STEP = 8;                 // tile entries a thread reads before it looks at them
 constexpr uint32_t RK_NO_ROW = 0xFFFFFFFFu;   // f of a tile entry behind B (a row index is below 2^31): ends every segment
-
-__device__ __forceinline__ int64_t clamp_row(int64_t r, int64_t B) { return r < 0 ? 0 : (r >= B ? B - 1 : r); }
-
-// fp32 -> uint32, ascending with the value: NaN -> 0 (below -inf, which maps to 0x007FFFFF), -0.0 -> the key of +0.0 (topn.hip's)
-__device__ __forceinline__ uint32_t order_key(float v) {
-    uint32_t u = rat_fbits(v);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // topn.hip's 64-bit key with the ROW in the place of the position inside the segment (a row is below 2^31): unique, and inside a
 // segment a before b iff key(a) > key(b) — larger value first, equal values by ascending row

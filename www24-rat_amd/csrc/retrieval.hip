@@ -17,7 +17,7 @@
 // best (rare after the first few hundred rows).  The 256 private lists are merged by K rounds of a work-group arg-max.
 // Ties: torch.topk leaves the order of equal scores unspecified (it differs between its CPU and CUDA kernels and with the
 // chunk size); this kernel is deterministic — equal scores keep the LOWER pool index.
-#include "rat_device.h"
+#include "bm25_scan.h"
 #include "../../include/rat_hip.h"
 
 namespace {
@@ -38,10 +38,6 @@ struct RetrArgs {
     int F, K;
 };
 
-__device__ __forceinline__ bool better(double sa, int64_t ia, double sb, int64_t ib) {   // (score desc, index asc)
-    return sa > sb || (sa == sb && ia < ib);
-}
-
 template <int KMAX, int QT, int RU>
 __global__ void __launch_bounds__(RT_THREADS) bm25_topk_kernel(RetrArgs a) {
     __shared__ double red_s[RT_THREADS];
@@ -52,17 +48,8 @@ __global__ void __launch_bounds__(RT_THREADS) bm25_topk_kernel(RetrArgs a) {
         const int64_t q0 = tile * QT;
         double val[QT][KMAX], kth[QT];                     // kth = score of the current K-th entry (0 while the list is not full)
         int64_t idx[QT][KMAX];
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            kth[t] = 0.0;
-#pragma unroll
-            for (int k = 0; k < KMAX; ++k) {
-                val[t][k] = 0.0;
-                idx[t][k] = -1;
-            }
-        }
-        // ---- scan: every lane walks its rows in increasing order, so among equal scores the lower index arrives first and a
-        //      later row must be STRICTLY better than the current K-th entry to get in
+        list_init<KMAX, QT>(val, idx, kth);
+        // ---- scan: every lane walks its rows in increasing order and offers them to its lists (bm25_scan.h: RAT_BM25_LIST_INSERT)
         for (int64_t n0 = tid; n0 < a.N; n0 += (int64_t)RT_THREADS * RU) {
             double s[RU][QT];
 #pragma unroll
@@ -104,25 +91,7 @@ __global__ void __launch_bounds__(RT_THREADS) bm25_topk_kernel(RetrArgs a) {
                 const int64_t n = n0 + (int64_t)u * RT_THREADS;
 #pragma unroll
                 for (int t = 0; t < QT; ++t) {
-                    if (s[u][t] > kth[t]) {                                               // positive AND strictly better than the K-th
-                        double cs = s[u][t];
-                        int64_t ci = n;
-                        bool placed = false;          // once the newcomer sits the rest only shifts down: a displaced entry is OLDER
-                                                      // (lower index) than the equal scores below it and must stay in front of them
-#pragma unroll
-                        for (int k = 0; k < KMAX; ++k) {
-                            if (k < a.K && (placed || cs > val[t][k])) {
-                                placed = true;
-                                const double ts = val[t][k];
-                                const int64_t ti = idx[t][k];
-                                val[t][k] = cs;
-                                idx[t][k] = ci;
-                                cs = ts;
-                                ci = ti;
-                            }
-                            if (k == a.K - 1) kth[t] = val[t][k];
-                        }
-                    }
+                    RAT_BM25_LIST_INSERT(KMAX, val[t], idx[t], kth[t], a.K, s[u][t], n);
                 }
             }
         }
@@ -148,15 +117,7 @@ __global__ void __launch_bounds__(RT_THREADS) bm25_topk_kernel(RetrArgs a) {
                 const double ws = red_s[0];
                 const int64_t wi = red_i[0];
                 __syncthreads();
-                if (wi >= 0 && idx[t][0] == wi) {                                          // the winner pops its head
-#pragma unroll
-                    for (int j = 0; j + 1 < KMAX; ++j) {
-                        val[t][j] = val[t][j + 1];
-                        idx[t][j] = idx[t][j + 1];
-                    }
-                    val[t][KMAX - 1] = 0.0;
-                    idx[t][KMAX - 1] = -1;
-                }
+                if (wi >= 0 && idx[t][0] == wi) list_pop<KMAX>(val[t], idx[t]);             // the winner pops its head
                 if (tid == 0 && q0 + t < a.Q) {
                     a.out_val[(q0 + t) * a.K + k] = wi >= 0 ? ws : 0.0;
                     a.out_idx[(q0 + t) * a.K + k] = wi;

@@ -6,12 +6,12 @@
 //
 //   rat_candidates_expand   out[b][l] = cand[b][w] where l == cols[w], otherwise ctx[f(b)][l]: the full rows of every candidate from
 //                           ONE context row per request (held at the request's head row) and the candidates' own columns.  One
-//                           launch; the inverse of `cols` is built in LDS by every work-group, rows move as 16-byte words when the
+//                           launch (order_common.h's expand_kernel); the inverse of `cols` is built in LDS by every work-group, rows move as 16-byte words when the
 //                           row width and the buffers allow.
 //   rat_topn_seg            per request the positions (inside the request) and values of its n largest predictions, in the order
 //                           np.argsort(-y_seg, kind="stable")[:n]: value descending, equal values (-0.0 and +0.0 tie) by ascending
 //                           position, NaN after every number.  Every candidate gets the 64-bit key
-//                               (order-preserving uint32 of y, NaN -> 0) << 32  |  0xFFFFFFFF - position
+//                               (order_common.h's order_key of y, NaN -> 0) << 32  |  0xFFFFFFFF - position
 //                           — unique inside a segment — and round k takes the largest key below the key of round k - 1: n rounds of
 //                           a work-group arg-max.  No floating-point arithmetic touches y, so out_val carries y's bits.
 //
@@ -24,8 +24,7 @@
 // that are, one after the other (a head's segment may reach far beyond the group's rows: it is read, never written).  The keys of a
 // segment's first TN_STAGE rows are staged in LDS while its end is searched; rows beyond are re-read from y in every round.
 // No atomics, no communication between work-groups, nothing allocated or read back: both kernels are captured into the serving graph.
-#include "rat_device.h"
-#include "../../include/rat_hip.h"
+#include "order_common.h"
 
 namespace {
 
@@ -33,17 +32,6 @@ constexpr int TN_THREADS = 256;
 constexpr int TN_WAVES = TN_THREADS / 64;
 constexpr int TN_ROWS = 16;                // batch rows per work-group
 constexpr int TN_STAGE = 1024;             // rows of a segment whose keys are kept in LDS
-constexpr int EX_MAX_L = 8192;             // the inverse column map is L words of LDS
-
-__device__ __forceinline__ int64_t clamp_row(int64_t r, int64_t B) { return r < 0 ? 0 : (r >= B ? B - 1 : r); }
-
-// fp32 -> uint32, ascending with the value: NaN -> 0 (below -inf, which maps to 0x007FFFFF), -0.0 -> the key of +0.0
-__device__ __forceinline__ uint32_t order_key(float v) {
-    uint32_t u = rat_fbits(v);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // the largest of the work-group's 256 keys, to every thread: shuffles inside a wave (two 32-bit halves), then one LDS word per wave
 // and ONE barrier.  `turn` counts the calls of this thread (the same for all threads): the slots are double-buffered by its parity,
@@ -146,44 +134,9 @@ struct ExpandArgs {
     int32_t* out;                // [B][L]
     int64_t B;
     int L, W;
+    // expand_kernel's (order_common.h) source of a candidate's own columns: the caller's tuple of row b
+    __device__ const int32_t* row(int64_t b, int64_t) const { return cand + b * W; }
 };
-
-// work item = one word (VEC: one 16-byte group of four) of out.  inv[l] = the w with cols[w] == l, or -1: built by every
-// work-group, L + W words of traffic against the 256+ words it then writes per trip
-template <bool VEC>
-__global__ void __launch_bounds__(256) candidates_expand_kernel(ExpandArgs a) {
-    RAT_DYN_SMEM(smem);
-    int32_t* inv = reinterpret_cast<int32_t*>(smem);
-    for (int l = threadIdx.x; l < a.L; l += 256) inv[l] = -1;
-    __syncthreads();
-    for (int w = threadIdx.x; w < a.W; w += 256) {
-        const int32_t c = a.cols[w];
-        if (c >= 0 && c < a.L) inv[c] = w;                                      // a column outside the row is skipped
-    }
-    __syncthreads();
-    const int per_row = VEC ? a.L / 4 : a.L;
-    const int64_t total = a.B * per_row;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int64_t b = e / per_row;
-        const int l = (int)(e % per_row) * (VEC ? 4 : 1);
-        const int64_t h = clamp_row(a.first_row[b], a.B);
-        const int32_t* c = a.cand + b * a.W;
-        if (VEC) {
-            rat_u4 v = *reinterpret_cast<const rat_u4*>(a.ctx + h * a.L + l);
-            const int w0 = inv[l], w1 = inv[l + 1], w2 = inv[l + 2], w3 = inv[l + 3];
-            if (w0 >= 0) v.x = (unsigned)c[w0];
-            if (w1 >= 0) v.y = (unsigned)c[w1];
-            if (w2 >= 0) v.z = (unsigned)c[w2];
-            if (w3 >= 0) v.w = (unsigned)c[w3];
-            *reinterpret_cast<rat_u4*>(a.out + b * a.L + l) = v;
-        } else {
-            const int w = inv[l];
-            a.out[b * a.L + l] = w >= 0 ? c[w] : a.ctx[h * a.L + l];
-        }
-    }
-}
-
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -202,16 +155,9 @@ extern "C" int rat_candidates_expand(const int32_t* ctx, const int32_t* cand, co
                                      int L, int W, int32_t* out, void* stream) {
     RAT_REQUIRE(ctx && cand && cols && first_row && out, "null pointer");
     RAT_REQUIRE(B >= 1 && B <= 0x7fffffffLL, "B must be in [1, 2^31 - 1]");
-    RAT_REQUIRE(L >= 1 && L <= EX_MAX_L, "L must be in [1, 8192]");
-    RAT_REQUIRE(W >= 1 && W <= EX_MAX_L, "W must be in [1, 8192]");
+    RAT_REQUIRE(L >= 1 && L <= EXPAND_MAX_L, "L must be in [1, 8192]");
+    RAT_REQUIRE(W >= 1 && W <= EXPAND_MAX_L, "W must be in [1, 8192]");
     ExpandArgs a{ctx, cand, cols, first_row, out, B, L, W};
-    const bool vec = L % 4 == 0 && al16(ctx) && al16(out);
-    const int64_t blocks = (B * (vec ? L / 4 : L) + 255) / 256;
-    const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
-    const size_t lds = (size_t)L * sizeof(int32_t);
-    if (vec)
-        RAT_LAUNCH(candidates_expand_kernel<true>, grid, 256, lds, stream, a);
-    else
-        RAT_LAUNCH(candidates_expand_kernel<false>, grid, 256, lds, stream, a);
+    expand_launch(a, stream);
     return rat_check_launch("rat_candidates_expand");
 }
