@@ -933,6 +933,34 @@ int rat_topn_merge(int32_t* run_item, float* run_val, int32_t* run_len, const in
                    const int64_t* heads, int64_t item0, const int32_t* ex_items, const int64_t* ex_offsets, int64_t E, int64_t R,
                    int64_t B, int n, void* stream);
 
+/* Candidate retrieval through posting lists (csrc/postings.hip; additive in ABI v9; rat_amd/online.py: build_postings,
+ * retrieve_shared) for requests whose rows share a context: the rows of a request equal each other on every used column outside the
+ * VARYING ones, vary_mask (bit f = used column f < n_fields varies; bits at or past n_fields are ignored).
+ *
+ * The index: post_ids / post_rows int32 [n_fields][capacity] hold, per used column, the ids and the rows of the pool rows
+ * [0, n_sorted) sorted by (id, row); n_sorted_dev is one int64 in device memory, clamped to [0, n].  The pool is taken in form
+ * RAT_POOL_HOST or RAT_POOL_DEV (db_ids_field_major [n_fields][capacity], capacity <= 2^31 - 1); RAT_POOL_RING is refused.
+ * ctx_indices int64 [n_ctx][topk] (-1 padded) holds, per request, the topk best indexed rows under the weights with the varying
+ * columns set to 0.0 — rat_bm25_topk_split_before over the requests' head rows with before = n_sorted —, and ctx_row int64 [n_qry]
+ * names the list of query b (clamped to [0, n_ctx)).
+ *
+ * Per query the candidates are (1) for each varying column, ascending, the posting list of the query's id (the range between a
+ * lower and an upper bound in post_ids), a row taken only if it equals the query in no earlier varying column; (2) the entries of
+ * its context list that equal it in no varying column; (3) the tail rows [n_sorted, n).  Every candidate is scored in full as
+ * rat_bm25_topk scores — fp64, (db == q) * idf, f ascending over all n_fields, score > 0 kept — and the outputs follow
+ * rat_bm25_topk's contract (fp64 [n_qry][topk], int64 [n_qry][topk] with -1 / 0.0 padding, int64 [n_qry]; score descending, index
+ * ascending).  With weights >= 0, the rows of a request equal outside the varying columns and the lists built as above, the result
+ * equals rat_bm25_topk over the live rows with the same qry_idf bit for bit.
+ *
+ * One launch on `stream`: no atomics, nothing allocated, synchronised or read back.  A posting row or context index outside
+ * [0, n_sorted) is skipped before it addresses anything: corrupt lists, counts or ctx_row give a wrong answer, never a wrong address.
+ * -1 + rat_last_error() and no launch on a null pointer, RAT_POOL_RING, n_fields or topk outside [1, 32], n_qry < 1, n_ctx < 1. */
+int rat_bm25_topk_postings(const int32_t* db_ids_field_major, int pool_form, const int64_t* header_dev, int64_t n_rows,
+                           int64_t capacity, const int32_t* post_ids, const int32_t* post_rows, const int64_t* n_sorted_dev,
+                           const int32_t* qry_ids, const double* qry_idf, uint32_t vary_mask, const int64_t* ctx_indices,
+                           const int64_t* ctx_row, int64_t n_ctx, double* out_values, int64_t* out_indices, int64_t* out_lens,
+                           int64_t n_qry, int n_fields, int topk, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,9 @@ pool, R in {1, 16} users against all M in {4096, 65536} items (the items differ 
 (i) a top_catalogue call plus reading items, y and lens back against the host loop — per chunk the rows expanded on the host, uploaded, a
 replayed score_requests, all predictions read back, a numpy merge — host clock + synchronise, one call per round, the sides alternating,
 results compared before anything is timed; (ii) the bytes both ways move per call, derived from the shapes.
+--catalogue --postings — additionally (profiles/online/postings_bench.txt) a third side, top_catalogue(postings=True), in the same rounds
+and compared bit for bit: (iii) the call against the other two, with build_postings() timed once; (iv) the parts of one 4096-row pass
+alone — the scan per row, the chain through the posting lists, the assembly and eval forward — as hipGraphs under device events.
 There is no CPU fallback: without a GPU the tool exits with an error."""
 import argparse
 import os
@@ -985,7 +988,7 @@ def part_rank(emit, quick):
     emit("   (%d fully-ranked graphs, %d bucket graphs)" % (len(scorer._rank_graphs), len(scorer._bucket_graphs)))
 
 
-def part_catalogue(emit, quick):
+def part_catalogue(emit, quick, postings=False):
     from rat_amd.online import OnlineScorer
     name, model, rows, vocab, cfg, n_pool, _capacity = _movielens(quick)
     min_s = 0.05 if quick else MIN_TIMED_MS / 1e3
@@ -1020,6 +1023,18 @@ def part_catalogue(emit, quick):
         items, val, lens = scorer.top_catalogue(contexts, n, chunk=chunk)
         return items.cpu().numpy(), val.cpu().numpy(), lens.cpu().numpy()
 
+    def postings_way(contexts, _cat, chunk):
+        items, val, lens = scorer.top_catalogue(contexts, n, chunk=chunk, postings=True)
+        return items.cpu().numpy(), val.cpu().numpy(), lens.cpu().numpy()
+
+    sides = [("catalogue", catalogue_way), ("host", host_way)]
+    if postings:
+        sides.insert(1, ("postings", postings_way))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        scorer.build_postings()
+        torch.cuda.synchronize()
+        t_build = (time.perf_counter() - t0) * 1e3
     results = []
     for M, R in grid:
         chunk = min(max(1, scorer.graph_max_batch // R), M)
@@ -1029,29 +1044,77 @@ def part_catalogue(emit, quick):
         for _ in range(scorer.graph_warmup + 1):
             got = catalogue_way(contexts, cat, chunk)
             want = host_way(contexts, cat, chunk)
+            if postings:
+                shared = postings_way(contexts, cat, chunk)
         torch.cuda.synchronize()
         same = all(np.array_equal(g.view(np.int32), w.view(np.int32)) for g, w in zip(got, want))
-        per = {"catalogue": [], "host": []}
+        same_p = postings and all(np.array_equal(g.view(np.int32), w.view(np.int32)) for g, w in zip(shared, got))
+        per = {label: [] for label, _fn in sides}
         while min(sum(v) for v in per.values()) / 1e6 < min_s or min(len(v) for v in per.values()) < 3:
-            for label, fn in (("catalogue", catalogue_way), ("host", host_way)):
+            for label, fn in sides:
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 fn(contexts, cat, chunk)
                 per[label].append((time.perf_counter() - t0) * 1e6)
-        results.append((M, R, chunk, per, same))
+        results.append((M, R, chunk, per, same, same_p))
     emit("== catalogue (i): one call [us], host clock: top_catalogue (per pass sweep expansion -> replayed score_requests -> rat_topn_seg -> "
          "rat_topn_merge, eager around the bucket graph) + items, y and lens read back, against the host loop: per chunk host expansion + "
          "upload + replayed score_requests + all predictions read back + numpy merge; one call per round, alternating; mean (min .. max)")
-    for M, R, chunk, per, same in results:
+    for M, R, chunk, per, same, _same_p in results:
         a, b = (sum(per[k]) / len(per[k]) for k in ("catalogue", "host"))
         emit("M %5d x R %2d (%3d passes of %4d) | catalogue %s | host %s | host / catalogue = %.2fx | results equal bit for bit: %s"
              % (M, R, (M + chunk - 1) // chunk, chunk, _stats(per["catalogue"]), _stats(per["host"]), b / a, same))
     emit("== catalogue (ii): bytes per call, derived from the shapes (L = %d, W = %d, n = %d; the catalogue itself, 4 M W bytes, goes up once, "
          "at set_catalogue)" % (L, W, n))
-    for M, R, chunk, _per, _same in results:
+    for M, R, chunk, _per, _same, _same_p in results:
         emit("M %5d x R %2d | H2D catalogue %6d (R L ids)  host %9d (R M L ids) | D2H catalogue %5d (R (8 n + 4))  host %8d (4 R M)"
              % (M, R, 4 * R * L, 4 * R * M * L, R * (8 * n + 4), 4 * R * M))
     emit("   (%d bucket graphs, no others: %s)" % (len(scorer._bucket_graphs), not (scorer._top_graphs or scorer._top_cand_graphs)))
+    if postings:
+        _catalogue_postings(emit, scorer, results, t_build, n_pool, vocab, cols, min_s)
+
+
+def _catalogue_postings(emit, scorer, results, t_build, n_pool, vocab, cols, min_s):
+    """the third side of part_catalogue, and the parts of one pass alone"""
+    from rat_amd import ops
+    emit("== catalogue (iii): top_catalogue(postings=True) in the same rounds [us] — per pass one scan per USER below n_sorted, then "
+         "rat_bm25_topk_postings over the rows, through bucket graphs of its own; build_postings() over the %d-row pool, once: %.1f ms "
+         "(8 F capacity = %d bytes of lists)" % (n_pool, t_build, 2 * scorer.index._post[0].numel() * 4))
+    for M, R, chunk, per, _same, same_p in results:
+        a, c = (sum(per[k]) / len(per[k]) for k in ("catalogue", "postings"))
+        apart = min(per["catalogue"]) > max(per["postings"])
+        emit("M %5d x R %2d (%3d passes of %4d) | postings %s | catalogue / postings = %.2fx | every postings round faster than every "
+             "catalogue round: %s | equal to top_catalogue() bit for bit: %s"
+             % (M, R, (M + chunk - 1) // chunk, chunk, _stats(per["postings"]), a / c, apart, same_p))
+    emit("   (%d bucket graphs, %d posting-list graphs)" % (len(scorer._bucket_graphs), len(scorer._postings_graphs)))
+    # one pass of P = graph_max_batch rows, its parts alone: R users x P / R items
+    P, index, dev = scorer.graph_max_batch, scorer.index, scorer.device
+    rs = np.random.RandomState(12)
+    emit("== catalogue (iv): the parts of one %d-row pass alone [us per pass]: hipGraphs of %d passes under device events, alternating"
+         % (P, 5))
+    for R in (1, 16):
+        m = P // R
+        ids = np.repeat(np.stack([rs.randint(0, v, size=R) for v in vocab], axis=1), m, axis=0).astype(np.int32)
+        for c in cols:
+            ids[:, c] = rs.randint(0, vocab[c], size=P)
+        ids = torch.from_numpy(ids).to(dev)
+        heads = torch.arange(R, dtype=torch.int64, device=dev) * m
+        first_row = heads[:, None].expand(R, m).reshape(-1).contiguous()
+        mask = index._varying_mask(cols)
+        _rows, labels = scorer._constants(P)
+        with torch.no_grad():
+            nbr = index.retrieve(ids, _first_row=first_row)
+            assert all(torch.equal(a, b) for a, b in zip(nbr, index._retrieve_shared(ids, first_row, heads, mask)))
+
+            def forward():
+                y_pred, _loss, _reg, _saved = scorer.model._run_forward(scorer._assemble_batch(ids, labels, nbr[1]), save=False, with_reg=False)
+                return y_pred
+            graphs = {"scan": _graph_of(lambda: index.retrieve(ids, _first_row=first_row), 5)[0],
+                      "lists": _graph_of(lambda: index._retrieve_shared(ids, first_row, heads, mask), 5)[0],
+                      "forward": _graph_of(forward, 5)[0]}
+        t = time_alternating(graphs, 5, min_s * 1e3)
+        emit("R %2d x %4d items | prepare + scan per row %8.1f | prepare + scan per user + posting lists %8.1f | assembly + eval forward %8.1f"
+             % (R, m, t["scan"] * 1e3, t["lists"] * 1e3, t["forward"] * 1e3))
 
 
 RANK_TOPN = 64                                                              # rat_topn_seg's largest page, beside the full ranking
@@ -1085,6 +1148,7 @@ def main():
     ap.add_argument("--top", action="store_true", help="measure each request's top-n candidates (rat_topn_seg alone; top_candidates against the host way)")
     ap.add_argument("--rank", action="store_true", help="measure each request's full ranking (rat_rank_seg alone; rank_requests against the host way)")
     ap.add_argument("--catalogue", action="store_true", help="measure the resident item catalogue (top_catalogue against the host loop over chunks)")
+    ap.add_argument("--postings", action="store_true", help="with --catalogue: top_catalogue(postings=True) as a third side, and the parts of a pass")
     ap.add_argument("--trace", action="store_true", help="with --delete: only a few deletions per point, for a kernel trace")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -1127,7 +1191,7 @@ def main():
         part_rank(emit, args.quick)
         return
     if args.catalogue:
-        part_catalogue(emit, args.quick)
+        part_catalogue(emit, args.quick, args.postings)
         return
     part1(emit, args.quick)
     part2(emit, args.quick)

@@ -196,6 +196,9 @@ _SIGNATURES = {
     "rat_catalogue_expand": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int64, c_int, c_int, c_int64, _P, _P]),
     "rat_topn_exclude": (c_int, [_P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, c_int64, _P, _P]),
     "rat_topn_merge": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, c_int64, c_int64, c_int64, c_int, _P]),
+    # candidate retrieval through posting lists, for requests whose rows share a context
+    "rat_bm25_topk_postings": (c_int, [_P, c_int, _P, c_int64, c_int64, _P, _P, _P, _P, _P, ctypes.c_uint32, _P, _P, c_int64, _P, _P, _P,
+                                       c_int64, c_int, c_int, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

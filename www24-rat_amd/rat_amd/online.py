@@ -109,6 +109,15 @@ swept in passes of ``chunk`` items per user — the sweep form of the expansion,
 a lookup in the merge).  The new kernels run eagerly around the chain; no graph class and no graph dictionary is new.  No ``same=`` /
 ``before=`` on these calls either.
 
+The candidates of a request are ONE context row with a few columns swapped, yet every candidate row scans the whole pool.
+``build_postings()`` keeps an inverted index over the pool — per used column the rows sorted by (id, row), built on the device — and
+``RetrievalIndex.retrieve_shared(ids, request_offsets, varying)`` uses it for such rows: one scan per REQUEST (its head row, the varying
+columns' weights at 0.0, over the indexed rows) gives the request's context list, and ``rat_bm25_topk_postings`` scores, per row, the
+posting lists of its ids in the varying columns, that list and the rows appended since the build — the scan's result bit for bit.
+``postings=True`` on ``top_candidates`` / ``rank_candidates`` / ``top_items`` / ``rank_items`` (their chain launched eagerly) and on
+``top_catalogue`` (its pass through ``_SharedGraph``, bucket graphs of its own in ``_postings_graphs``) retrieves that way; the
+default, ``False``, is the code as it was, launch for launch.  Served on the immutable and the ``capacity=`` pool, not on a window.
+
 Not served online (refused at construction): the config keys ``exact_match_cols`` / ``exact_match_col_indices`` (the restriction is
 per call, ``same=``; not built: ``same`` with ``request_offsets``, and all used columns exact), label-wise retrieval, topK > 32, more
 than 32 retrieval columns, data-parallel models.  Rows are deleted from a
@@ -451,6 +460,118 @@ class RetrievalIndex:
     def __len__(self):
         return self.n_db
 
+    # ---- requests that share a context: posting lists -----------------------------------------------------------------------
+    _post = None                       # build_postings: (post_ids int32 [F, capacity], post_rows int32 [F, capacity], n_sorted int64 [1])
+    _n_sorted_host = None
+
+    @property
+    def postings_rows(self):
+        """the number of rows the posting lists cover (the pool's size at the last ``build_postings``), None before a build; rows
+        appended since are the TAIL, which ``retrieve_shared`` scores one by one until the next build"""
+        return self._n_sorted_host
+
+    def build_postings(self):
+        """The inverted index ``retrieve_shared`` reads: per used column the live rows sorted stably by (id, row) — the ids in
+        ``post_ids``, the rows in ``post_rows`` — and their number in device memory.  Built on the device (one stable sort over
+        ``db_t``'s live part), ordered with the requests on the current stream.  The buffers are allocated once, at the pool's capacity
+        (8 F capacity bytes); a later call sorts into the same buffers and rewrites the count, so captured graphs stay valid.
+        ValueError for a ``window=True`` pool: evictions and deletions renumber the rows the lists would hold."""
+        if self.window:
+            raise ValueError("build_postings: a window=True pool is not served (evictions and deletions renumber the rows the posting "
+                             "lists hold)")
+        if self._post is None:
+            self._post = (torch.zeros_like(self.db_t), torch.zeros_like(self.db_t), torch.zeros(1, dtype=torch.int64, device=self.device))
+            self._keep = {}            # vary mask -> bool [F], False at the varying columns
+        post_ids, post_rows, n_sorted = self._post
+        n = self.n_db
+        ids, order = torch.sort(self.db_t[:, :n], dim=1, stable=True)          # equal ids keep ascending rows
+        post_ids[:, :n].copy_(ids)
+        post_rows[:, :n].copy_(order)
+        n_sorted.fill_(n)
+        self._n_sorted_host = n
+
+    def _varying_mask(self, varying, what="retrieve_shared"):
+        """column numbers of the encoded row -> bit f set = used column f is among them (a column the index does not use cannot
+        change a retrieval and is dropped), or ValueError: no posting lists, or not a non-empty 1-D list of distinct columns in [0, L)"""
+        if self.window:
+            raise ValueError("%s: a window=True pool has no posting lists (its rows are renumbered by evictions and deletions)" % what)
+        if self._post is None:
+            raise ValueError("%s: no posting lists are built (build_postings())" % what)
+        try:
+            cols = _candidate_cols(varying, self.row_len)
+        except ValueError as exc:
+            raise ValueError("%s: varying: %s" % (what, exc)) from None
+        return sum(1 << f for f, c in enumerate(self._col_list) if c in cols)
+
+    def _keep_columns(self, mask):
+        """bool [F] on the device: False at the varying columns (one upload per mask, kept: a captured chain reads it)"""
+        keep = self._keep.get(mask)
+        if keep is None:
+            keep = self._keep[mask] = torch.tensor([not (mask >> f) & 1 for f in range(len(self._col_list))]).to(self.device)
+        return keep
+
+    def _retrieve_shared(self, ids, first_row, heads, mask):
+        """prepare over all rows -> the head rows' queries with the varying weights at 0.0 -> the scan over the R of them, below
+        n_sorted: the context lists T -> rat_bm25_topk_postings.  first_row int64 [B] and heads int64 [R] (ascending, the rows that
+        open the requests) on the device; nothing is read back"""
+        post_ids, post_rows, n_sorted = self._post
+        form = self._pool_form()
+        qry_ids, qry_idf = ops.bm25_query_prepare(ids, self.cols, self.table_ids, self.table_idf, self.table_offsets, first_row=first_row,
+                                                  lib=self._lib)
+        head_ids = qry_ids.index_select(0, heads)
+        head_idf = torch.where(self._keep_columns(mask), qry_idf.index_select(0, heads), 0.0)
+        _values, ctx, _lens = ops.bm25_topk_split(self.db_t, head_ids, head_idf, self.topK, splits=self.splits,
+                                                  before=n_sorted.expand(heads.numel()).contiguous(), lib=self._lib, **form)
+        ctx_row = torch.searchsorted(heads, first_row)
+        return ops.bm25_topk_postings(self.db_t, post_ids, post_rows, n_sorted, qry_ids, qry_idf, mask, ctx, ctx_row,
+                                      header=form.get("header"), n_rows=form.get("n_rows"), lib=self._lib)
+
+    def retrieve_shared(self, ids, request_offsets, varying, same=None, before=None):
+        """``retrieve(ids, request_offsets)`` — the same values, indices and lens, bit for bit — for requests whose rows SHARE A
+        CONTEXT: inside a request the rows differ only in the columns ``varying`` (column numbers of the encoded row, as ``cols`` of
+        ``OnlineScorer.top_candidates``; entries that are not used columns do not affect a retrieval and are dropped).  Instead of one
+        scan of the pool per row: one scan per REQUEST — its head row with the varying columns' weights at 0.0, over the rows the
+        posting lists cover —, then per row the posting lists of its ids in the varying columns, the request's list and the rows
+        appended since ``build_postings`` (``rat_bm25_topk_postings``).  Needs ``build_postings()``.
+        PRECONDITION: the rows of a request are equal on every used column outside ``varying``.  Host ids with host offsets are
+        validated (ValueError, nothing launched); device ids are used unread, and rows that break the precondition then get the
+        neighbours of a request that kept it — a wrong answer, never a wrong address.
+        ``same`` / ``before`` are not offered here (ValueError), nor is a ``window=True`` pool."""
+        if same is not None or before is not None:
+            raise ValueError("retrieve_shared: same= and before= are not offered for requests that share a context")
+        mask = self._varying_mask(varying)
+        on_host = not (torch.is_tensor(ids) and ids.is_cuda)
+        host = None
+        if on_host:
+            host = ids.detach().numpy() if torch.is_tensor(ids) else np.asarray(ids)
+            if host.ndim != 2:
+                raise ValueError("ids must be [B, L] encoded rows, got shape %s" % (tuple(host.shape),))
+            B, L = host.shape
+        else:
+            if ids.ndim != 2:
+                raise ValueError("ids must be [B, L] encoded rows, got shape %s" % (tuple(ids.shape),))
+            B, L = ids.shape
+        if L != self.row_len:
+            raise ValueError("ids have %d columns, the pool's rows have %d" % (L, self.row_len))
+        if B == 0:
+            raise ValueError("empty request")
+        off_host, off_dev = _request_offsets(request_offsets, B)
+        if host is not None and off_host is not None:
+            fixed = [c for f, c in enumerate(self._col_list) if not (mask >> f) & 1]
+            first = np.repeat(off_host[:-1], np.diff(off_host))
+            differ = (host[:, fixed] != host[first][:, fixed]).any(axis=1)
+            if differ.any():
+                b = int(np.nonzero(differ)[0][0])
+                raise ValueError("retrieve_shared: row %d differs from the row that opens its request (row %d) in a used column outside "
+                                 "varying: the rows of a request must share their context" % (b, int(first[b])))
+        ids = _as_device_ids(ids, self.device)
+        first_row = _first_rows(off_host, off_dev, B, self.device)
+        if off_host is not None:
+            heads = torch.from_numpy(np.ascontiguousarray(off_host[:-1])).to(self.device, non_blocking=True)
+        else:
+            heads = off_dev[:-1].clamp(0, B - 1).contiguous()
+        return self._retrieve_shared(ids, first_row, heads, mask)
+
     # ---- the growable form -------------------------------------------------------------------------------------------
     def _init_growable(self, db, capacity):
         if capacity < len(db):
@@ -705,6 +826,21 @@ class _BucketGraph(_ChainGraph):
         return self.y_pred
 
 
+class _SharedGraph(_BucketGraph):
+    """``_BucketGraph`` over the chain of requests that share a context (``RetrievalIndex._retrieve_shared`` instead of the scan per
+    row), for one mask of varying columns: ids, first_row and the rows that open the requests are the static inputs, all refreshed
+    from device tensors before each replay"""
+
+    def __init__(self, scorer, mask, ids, first_row, heads):
+        _ChainGraph.__init__(self, lambda i, f, h: scorer._score_eager(i, f, shared=(mask, h)), ids, first_row, heads)
+
+    def run(self, ids, first_row, heads):
+        for static, t in zip(self.static, (ids, first_row, heads)):
+            static.copy_(t, non_blocking=True)
+        self.graph.replay()
+        return self.y_pred
+
+
 class _HeadRows:
     """the rows that open the requests, as the ranked calls gather them: a device tensor is passed through, a host array is uploaded
     only when it differs from the last one (the same request sizes again)"""
@@ -824,6 +960,8 @@ class OnlineScorer:
         self._cols_dev = {}            # top_candidates / rank_candidates: the candidate columns as a tuple -> the same as an int32 device tensor
         self._found = None             # relabel_where's index list (one entry per row the pool can hold), from its first call on
         self._catalogue = None         # set_catalogue: (items int32 [M, W] on the device, the columns as an int32 device tensor)
+        self._catalogue_cols = None    # ... and the columns as a tuple
+        self._postings_graphs = {}     # top_catalogue(postings=True): (bucket, ..., the columns, requests) -> [eager passes seen, _SharedGraph | False | None]
 
     # ------------------------------------------------------------------------------------------------------------------
     def _constants(self, B):
@@ -841,14 +979,32 @@ class OnlineScorer:
         rows, _zeros = self._constants(ids.shape[0])
         return ops.batch_assemble(ids, labels, self.pool_ids, self.pool_labels, neighbours, rows, lib=self._lib, **form)
 
-    def _assemble(self, ids, first_row=None, same=None):
+    def _assemble(self, ids, first_row=None, same=None, shared=None):
+        """``shared`` = (mask of varying used columns, heads int64 [R] on the device): the requests share a context, and the neighbours
+        come through the posting lists (``RetrievalIndex._retrieve_shared``) — the same lists, bit for bit"""
         _rows, labels = self._constants(ids.shape[0])
-        _values, indices, _lens = self.index.retrieve(ids, _first_row=first_row, _exact=same)
+        if shared is not None:
+            _values, indices, _lens = self.index._retrieve_shared(ids, first_row, shared[1], shared[0])
+        else:
+            _values, indices, _lens = self.index.retrieve(ids, _first_row=first_row, _exact=same)
         return self._assemble_batch(ids, labels, indices)                      # the neighbour lists: the scan's own index output
 
-    def _score_eager(self, ids, first_row=None, same=None):
-        y_pred, _loss, _reg, _saved = self.model._run_forward(self._assemble(ids, first_row, same), save=False, with_reg=False)
+    def _score_eager(self, ids, first_row=None, same=None, shared=None):
+        y_pred, _loss, _reg, _saved = self.model._run_forward(self._assemble(ids, first_row, same, shared), save=False, with_reg=False)
         return y_pred.reshape(-1)
+
+    def build_postings(self):
+        """``RetrievalIndex.build_postings``: the posting lists that ``postings=True`` retrieves through (``top_candidates``,
+        ``rank_candidates``, ``top_items``, ``rank_items``, ``top_catalogue``).  Rows appended afterwards are served as the lists'
+        tail; a second call covers them.  Captured graphs stay valid.  ValueError for a ``window=True`` pool."""
+        self.index.build_postings()
+
+    def _shared_mask(self, cols, postings, what):
+        """``postings`` as a call takes it -> None (False: today's chain), or the mask of the used columns among ``cols`` — ValueError
+        before any entry point without ``build_postings()`` or on a window pool"""
+        if not postings:
+            return None
+        return self.index._varying_mask(cols, "%s(postings=True)" % what)
 
     def append(self, rows):
         """``RetrievalIndex.append`` plus the row store (ids and labels of the new rows, the same launch).  Afterwards the scorer equals
@@ -1182,14 +1338,14 @@ class OnlineScorer:
                               "the batched online requests")
 
     # ---- each request's best candidates ----------------------------------------------------------------------------------------
-    def _top_eager(self, ids, first_row, n):
+    def _top_eager(self, ids, first_row, n, shared=None):
         """the request chain, then rat_topn_seg over its predictions -> (pos [B, n], val [B, n], lens [B], y_pred [B]); rows that open
         no request hold padding"""
-        y_pred = self._score_eager(ids, first_row).contiguous()
+        y_pred = self._score_eager(ids, first_row, shared=shared).contiguous()
         return ops.topn_seg(y_pred, first_row, n, lib=self._lib) + (y_pred,)
 
-    def _top_cand_eager(self, slab, cand, cols_dev, first_row, n):
-        return self._top_eager(ops.candidates_expand(slab, cand, cols_dev, first_row, lib=self._lib), first_row, n)
+    def _top_cand_eager(self, slab, cand, cols_dev, first_row, n, shared=None):
+        return self._top_eager(ops.candidates_expand(slab, cand, cols_dev, first_row, lib=self._lib), first_row, n, shared)
 
     def _heads(self, off_host, off_dev, B, pad, upload=True):
         """the rows that open the requests, int64 [R] on the device (``pad``: and row B, which opens the pad request).  Device offsets
@@ -1280,21 +1436,30 @@ class OnlineScorer:
         slab = self._slab(contexts, self._heads(off_host, off_dev, C, False), C)
         return ops.candidates_expand(slab, candidates, cols_dev, _first_rows(off_host, off_dev, C, self.device), lib=self._lib)
 
-    def top_candidates(self, contexts, candidates, cols, request_offsets, n, scores=False):
+    def top_candidates(self, contexts, candidates, cols, request_offsets, n, scores=False, postings=False):
         """``top_requests`` for requests given as ONE context row each plus the columns in which their candidates differ:
         ``contexts`` [R, L] encoded rows (their ``cols`` entries are ignored), ``candidates`` [C, W] the ids of the columns ``cols``
         (W distinct column numbers of the encoded row) of all C candidates, ``request_offsets`` [R + 1] over the candidates (host:
         validated; device: used unread).  The caller uploads R L + C W ids instead of C L: the rows are built on the device
         (``rat_candidates_expand``, after one indexed copy of the contexts to the rows that open their requests), and the rest is
         ``top_requests``' chain.  Returns what ``top_requests`` returns, positions counting the candidates of a request from 0.
-        With ``graph=True`` the chain of a (bucket, n, cols) triple is captured into ``_top_cand_graphs``."""
+        With ``graph=True`` the chain of a (bucket, n, cols) triple is captured into ``_top_cand_graphs``.
+        ``postings=True`` (needs ``build_postings()``; not on a window pool): the candidates of a request share its context and differ
+        in ``cols``, so the neighbours are retrieved through the posting lists (``RetrievalIndex.retrieve_shared``'s chain with
+        ``varying = cols``) — the same result bit for bit, launched eagerly."""
         if self.model.training:
             raise RuntimeError("OnlineScorer.top_candidates needs the model in eval mode (model.eval())")
         n = _top_n(n)
+        mask = self._shared_mask(cols, postings, "top_candidates")
         contexts, cand, cols, cols_dev, off_host, off_dev = self._candidates(contexts, candidates, cols, request_offsets)
         C = cand.shape[0]
         with torch.no_grad():
             P = 1 << (C - 1).bit_length()
+            if mask is not None:
+                heads = self._heads(off_host, off_dev, C, False)
+                out = self._top_cand_eager(self._slab(contexts, heads, C), cand, cols_dev, _first_rows(off_host, off_dev, C, self.device), n,
+                                           shared=(mask, heads))
+                return self._top_result(out, heads, C, scores)
             if not (self.graph and cand.is_cuda and P <= self.graph_max_batch):
                 slab = self._slab(contexts, self._heads(off_host, off_dev, C, False), C)
                 out = self._top_cand_eager(slab, cand, cols_dev, _first_rows(off_host, off_dev, C, self.device), n)
@@ -1317,13 +1482,13 @@ class OnlineScorer:
             return self._top_result(out, heads[:-1] if P > C else heads, C, scores)
 
     # ---- each request's full ranking ---------------------------------------------------------------------------------------------
-    def _rank_eager(self, ids, first_row):
+    def _rank_eager(self, ids, first_row, shared=None):
         """the request chain, then rat_rank_seg over its predictions -> (order [B], val [B], rank [B], y_pred [B])"""
-        y_pred = self._score_eager(ids, first_row).contiguous()
+        y_pred = self._score_eager(ids, first_row, shared=shared).contiguous()
         return ops.rank_seg(y_pred, first_row, lib=self._lib) + (y_pred,)
 
-    def _rank_cand_eager(self, slab, cand, cols_dev, first_row):
-        return self._rank_eager(ops.candidates_expand(slab, cand, cols_dev, first_row, lib=self._lib), first_row)
+    def _rank_cand_eager(self, slab, cand, cols_dev, first_row, shared=None):
+        return self._rank_eager(ops.candidates_expand(slab, cand, cols_dev, first_row, lib=self._lib), first_row, shared)
 
     @staticmethod
     def _rank_result(out, B, offsets, scores):
@@ -1357,19 +1522,25 @@ class OnlineScorer:
             out = g.run(ids, first_row) if g is not None else self._rank_eager(ids, self._on_device(first_row))
             return self._rank_result(out, B, offsets, scores)
 
-    def rank_candidates(self, contexts, candidates, cols, request_offsets, scores=False):
+    def rank_candidates(self, contexts, candidates, cols, request_offsets, scores=False, postings=False):
         """``rank_requests`` for requests given as ``top_candidates`` takes them — ONE context row each (``contexts`` [R, L]) plus the
         columns ``cols`` in which their candidates differ (``candidates`` [C, W], ``request_offsets`` [R + 1] over the candidates) —
         without n: ``rat_candidates_expand`` after one indexed copy of the contexts, then ``rank_requests``' chain.  Returns what
         ``rank_requests`` returns, positions counting the candidates of a request from 0.  With ``graph=True`` the chain of a
-        (bucket, cols) pair is captured into ``_rank_cand_graphs``."""
+        (bucket, cols) pair is captured into ``_rank_cand_graphs``.  ``postings=True``: as ``top_candidates`` takes it."""
         if self.model.training:
             raise RuntimeError("OnlineScorer.rank_candidates needs the model in eval mode (model.eval())")
+        mask = self._shared_mask(cols, postings, "rank_candidates")
         contexts, cand, cols, cols_dev, off_host, off_dev = self._candidates(contexts, candidates, cols, request_offsets)
         C = cand.shape[0]
         offsets = torch.from_numpy(off_host) if off_host is not None else off_dev
         with torch.no_grad():
             P = 1 << (C - 1).bit_length()
+            if mask is not None:
+                heads = self._heads(off_host, off_dev, C, False)
+                out = self._rank_cand_eager(self._slab(contexts, heads, C), cand, cols_dev, _first_rows(off_host, off_dev, C, self.device),
+                                            shared=(mask, heads))
+                return self._rank_result(out, C, offsets, scores)
             if not (self.graph and cand.is_cuda and P <= self.graph_max_batch):
                 slab = self._slab(contexts, self._heads(off_host, off_dev, C, False), C)
                 out = self._rank_cand_eager(slab, cand, cols_dev, _first_rows(off_host, off_dev, C, self.device))
@@ -1414,6 +1585,7 @@ class OnlineScorer:
                 raise ValueError("the catalogue must hold integers, got dtype %s" % host.dtype)
             cat = torch.from_numpy(np.ascontiguousarray(retrieval._as_int32(host, "catalogue"))).to(self.device)
         self._catalogue = (cat, self._cols_tensor(cols))
+        self._catalogue_cols = cols
 
     @property
     def catalogue_size(self):
@@ -1462,26 +1634,46 @@ class OnlineScorer:
         ids = ops.catalogue_expand(slab, cat, cols_dev, _first_rows(off_host, off_dev, C, self.device), items=idx, lib=self._lib)
         return ids, off_host if off_host is not None else off_dev
 
-    def top_items(self, contexts, items, request_offsets, n, scores=False):
+    def _shared_items(self, request, mask):
+        """what ``_item_requests`` returns -> (ids, first_row, heads, the offsets as a tensor, shared) for the eager chains"""
+        ids, off = request
+        off_host, off_dev = (None, off) if torch.is_tensor(off) else (off, None)
+        C = ids.shape[0]
+        heads = self._heads(off_host, off_dev, C, False)
+        offsets = torch.from_numpy(off_host) if off_host is not None else off_dev
+        return ids, _first_rows(off_host, off_dev, C, self.device), heads, offsets, (mask, heads)
+
+    def top_items(self, contexts, items, request_offsets, n, scores=False, postings=False):
         """``top_candidates`` with the candidates given as INDICES into the catalogue: ``contexts`` [R, L] encoded rows (their entries in
         the catalogue's columns are ignored), ``items`` [C] catalogue indices (host: validated, every entry in [0, M); device: used
         unread, clamped), ``request_offsets`` [R + 1] over them.  C indices go up instead of C W ids.  The rows are built on the device
         (``rat_catalogue_expand``, after one indexed copy of the contexts) and handed to ``top_requests`` as a pair of device ids and
         the offsets, so its chain and its captured graphs are shared with direct callers.  Returns what ``top_candidates`` returns,
-        positions counting a request's items from 0."""
+        positions counting a request's items from 0.  ``postings=True``: as ``top_candidates`` takes it, the varying columns being the
+        catalogue's; the chain is launched eagerly."""
         if self.model.training:
             raise RuntimeError("OnlineScorer.top_items needs the model in eval mode (model.eval())")
         n = _top_n(n)
+        mask = self._shared_mask(self._catalogue_cols, postings, "top_items") if self._catalogue is not None else None
         with torch.no_grad():
-            return self.top_requests(self._item_requests(contexts, items, request_offsets, "top_items"), n, scores=scores)
+            request = self._item_requests(contexts, items, request_offsets, "top_items")
+            if mask is None:
+                return self.top_requests(request, n, scores=scores)
+            ids, first_row, heads, _offsets, shared = self._shared_items(request, mask)
+            return self._top_result(self._top_eager(ids, first_row, n, shared), heads, ids.shape[0], scores)
 
-    def rank_items(self, contexts, items, request_offsets, scores=False):
+    def rank_items(self, contexts, items, request_offsets, scores=False, postings=False):
         """``rank_candidates`` with the candidates given as indices into the catalogue (as ``top_items`` takes them), through
-        ``rank_requests``' chain.  Returns what ``rank_candidates`` returns."""
+        ``rank_requests``' chain.  Returns what ``rank_candidates`` returns.  ``postings=True``: as ``top_items`` takes it."""
         if self.model.training:
             raise RuntimeError("OnlineScorer.rank_items needs the model in eval mode (model.eval())")
+        mask = self._shared_mask(self._catalogue_cols, postings, "rank_items") if self._catalogue is not None else None
         with torch.no_grad():
-            return self.rank_requests(self._item_requests(contexts, items, request_offsets, "rank_items"), scores=scores)
+            request = self._item_requests(contexts, items, request_offsets, "rank_items")
+            if mask is None:
+                return self.rank_requests(request, scores=scores)
+            ids, first_row, _heads, offsets, shared = self._shared_items(request, mask)
+            return self._rank_result(self._rank_eager(ids, first_row, shared), ids.shape[0], offsets, scores)
 
     def _exclusion(self, exclude, R, M):
         """what ``top_catalogue`` takes as ``exclude`` -> (ex_items int32 [E], ex_offsets int64 [R + 1]) on the device.  Host lists are
@@ -1514,7 +1706,25 @@ class OnlineScorer:
         return (torch.from_numpy(np.ascontiguousarray(ordered)).to(self.device, non_blocking=True),
                 torch.from_numpy(np.ascontiguousarray(off)).to(self.device, non_blocking=True))
 
-    def top_catalogue(self, contexts, n, chunk=None, exclude=None, scores=False):
+    def _score_shared(self, ids, first_row, heads, padded, cols, mask):
+        """``score_requests`` over device ids for requests that share a context -> y_pred fp32 [B]: the chain through the posting
+        lists, padded to the bucket as ``score_requests`` pads (``padded``: first_row and heads with the pad request, or None when the
+        rows fill the bucket), captured per (bucket, eval key, cols, requests) in ``_postings_graphs`` — the rows that open the
+        requests are a static input of the chain, so their number is part of its shape"""
+        B = ids.shape[0]
+        P = 1 << (B - 1).bit_length()
+        if not (self.graph and ids.is_cuda and P <= self.graph_max_batch):
+            return self._score_eager(ids, first_row, shared=(mask, heads))
+        if P > B:                                                              # the pad rows: copies of the first row, a request of their own
+            ids = torch.cat([ids, ids[:1].expand(P - B, -1)])
+            first_row, heads = padded
+        key = (P, self.model._eval_graph_key((P, self.index.topK + 1, ids.shape[1])), cols, heads.numel())
+        g = self._captured(self._postings_graphs, key, lambda: _SharedGraph(self, mask, ids, first_row, heads),
+                           "the batched online requests that share a context")
+        y_pred = g.run(ids, first_row, heads) if g is not None else self._score_eager(ids, first_row, shared=(mask, heads))
+        return y_pred[:B].clone()
+
+    def top_catalogue(self, contexts, n, chunk=None, exclude=None, scores=False, postings=False):
         """The best ``n`` items of the WHOLE catalogue for each of R users: ``contexts`` [R, L] encoded rows -> device tensors (items
         int32 [R, n], catalogue indices, best first, -1 padded; y fp32 [R, n] their predictions; lens int32 [R]) — per request
         ``np.argsort(-y_r, kind="stable")[:n]`` over its M predictions, equal predictions by ascending index.  ``scores=True``:
@@ -1526,11 +1736,16 @@ class OnlineScorer:
         ("what the user has already seen").  On the host the lists are validated and sorted per request (repeats allowed, entries in
         [0, M)); on the device they are used unread and must be sorted per request.  Excluded items keep their real values in the full
         predictions.  Limit: with ``exclude``, the result equals the reference order for predictions that are not NaN; an excluded
-        item is never returned, NaN-valued items may be missing from the tail of a page."""
+        item is never returned, NaN-valued items may be missing from the tail of a page.
+        ``postings=True`` (needs ``build_postings()``; not on a window pool): every pass retrieves through the posting lists — one scan
+        per user instead of one per (user, item), ``RetrievalIndex.retrieve_shared``'s chain with the catalogue's columns varying —
+        with the same results bit for bit; with ``graph=True`` the pass runs through bucket graphs of its own (``_postings_graphs``),
+        and ``score_requests``' are not touched."""
         if self.model.training:
             raise RuntimeError("OnlineScorer.top_catalogue needs the model in eval mode (model.eval())")
         n = _top_n(n)
         cat, cols_dev, R = self._catalogue_contexts(contexts, "top_catalogue")
+        mask = self._shared_mask(self._catalogue_cols, postings, "top_catalogue")
         M = cat.shape[0]
         if chunk is None:
             chunk = max(1, self.graph_max_batch // R)
@@ -1547,15 +1762,22 @@ class OnlineScorer:
             run_len = torch.zeros((R,), dtype=torch.int32, device=self.device)
             full = torch.empty((R, M), dtype=torch.float32, device=self.device) if scores else None
             requests = torch.arange(R + 1, dtype=torch.int64, device=self.device)
-            plans = {}                                                         # items per request -> (offsets, heads, first_row): two sizes at most
+            plans = {}                                                         # items per request -> (offsets, heads, first_row, those with a pad request): two sizes at most
             for i0 in range(0, M, chunk):
                 m = min(chunk, M - i0)
                 if m not in plans:
                     off = requests * m
-                    plans[m] = (off, off[:-1].contiguous(), off[:-1, None].expand(R, m).reshape(-1).contiguous())    # (R = 1: the reshape is a view of stride 0)
-                off, heads, first_row = plans[m]
+                    first_row = off[:-1, None].expand(R, m).reshape(-1).contiguous()                   # (R = 1: the reshape is a view of stride 0)
+                    padded, P = None, 1 << (R * m - 1).bit_length()
+                    if mask is not None and P > R * m:                         # postings: and with the pad request, which opens at row R m
+                        padded = (torch.cat([first_row, off[-1:].expand(P - R * m)]), off)
+                    plans[m] = (off, off[:-1].contiguous(), first_row, padded)
+                off, heads, first_row, padded = plans[m]
                 ids = ops.catalogue_expand(self._slab(contexts, heads, R * m), cat, cols_dev, first_row, item0=i0, lib=self._lib)
-                y_pred = self.score_requests((ids, off))[0].contiguous()
+                if mask is not None:
+                    y_pred = self._score_shared(ids, first_row, heads, padded, self._catalogue_cols, mask).contiguous()
+                else:
+                    y_pred = self.score_requests((ids, off))[0].contiguous()
                 ranked = y_pred if ex_items is None else ops.topn_exclude(y_pred, first_row, i0, m, ex_items, ex_off, lib=self._lib)
                 pos, val, lens = ops.topn_seg(ranked, first_row, n, lib=self._lib)
                 ops.topn_merge(run_item, run_val, run_len, pos, val, lens, heads, i0, ex_items, ex_off, lib=self._lib)

@@ -1430,3 +1430,50 @@ def topn_merge(run_item, run_val, run_len, pos, val, lens, heads, item0, ex_item
         E = ex_items.numel()
     lib.call("rat_topn_merge", _p(run_item), _p(run_val), _p(run_len), _p(pos), _p(val), _p(lens), _p(heads), int(item0),
              _p(ex_items) if E else None, _p(ex_offsets) if E else None, E, R, pos.shape[0], n, _stream(run_item))
+
+
+# ----------------------------------------------------------------------------- candidate retrieval through posting lists
+def bm25_topk_postings(db_t, post_ids, post_rows, n_sorted, qry_ids, qry_idf, vary_mask, ctx_indices, ctx_row, header=None,
+                       n_rows=None, lib=None):
+    """rat_bm25_topk's result for queries whose requests share a context, from posting lists instead of a scan (include/rat_hip.h:
+    rat_bm25_topk_postings) -> (values fp64 [Q, K], indices int64 [Q, K], lens int64 [Q]).  db_t, post_ids, post_rows int32
+    [F, capacity]; n_sorted int64 [1]; qry_ids int32 / qry_idf fp64 [Q, F]; vary_mask: bit f = used column f varies inside a request;
+    ctx_indices int64 [R, K], the requests' context lists (K = its width); ctx_row int64 [Q], the list of every query.  The pool's
+    form as in _pool_form, without ``ring``.  Shapes, dtypes, devices and contiguity are checked; no content is read."""
+    lib = lib or get_lib()
+    for t, dtype, name in ((db_t, torch.int32, "db_t"), (post_ids, torch.int32, "post_ids"), (post_rows, torch.int32, "post_rows"),
+                           (n_sorted, torch.int64, "n_sorted"), (qry_ids, torch.int32, "qry_ids"), (qry_idf, torch.float64, "qry_idf"),
+                           (ctx_indices, torch.int64, "ctx_indices"), (ctx_row, torch.int64, "ctx_row")):
+        if not torch.is_tensor(t):
+            raise TypeError("bm25_topk_postings: %s must be a tensor" % name)
+        _chk(t, dtype, name)
+    if db_t.ndim != 2 or not 1 <= db_t.shape[0] <= 32 or db_t.shape[1] < 1:
+        raise ValueError("bm25_topk_postings: db_t must be [F, capacity] with 1 <= F <= 32, got shape %s" % (tuple(db_t.shape),))
+    F, capacity = db_t.shape
+    if tuple(post_ids.shape) != (F, capacity) or tuple(post_rows.shape) != (F, capacity):
+        raise ValueError("bm25_topk_postings: post_ids and post_rows must be [%d, %d] as db_t, got shapes %s, %s"
+                         % (F, capacity, tuple(post_ids.shape), tuple(post_rows.shape)))
+    if n_sorted.numel() < 1:
+        raise ValueError("bm25_topk_postings: n_sorted must hold one int64")
+    if qry_ids.ndim != 2 or qry_ids.shape[0] < 1 or qry_ids.shape[1] != F or qry_idf.shape != qry_ids.shape:
+        raise ValueError("bm25_topk_postings: qry_ids and qry_idf must be [Q, %d], got shapes %s, %s"
+                         % (F, tuple(qry_ids.shape), tuple(qry_idf.shape)))
+    Q = qry_ids.shape[0]
+    if ctx_indices.ndim != 2 or ctx_indices.shape[0] < 1 or not 1 <= ctx_indices.shape[1] <= 32:
+        raise ValueError("bm25_topk_postings: ctx_indices must be [R, K] with R >= 1 and 1 <= K <= 32, got shape %s"
+                         % (tuple(ctx_indices.shape),))
+    R, K = ctx_indices.shape
+    if tuple(ctx_row.shape) != (Q,):
+        raise ValueError("bm25_topk_postings: ctx_row must be [%d], got shape %s" % (Q, tuple(ctx_row.shape)))
+    if isinstance(vary_mask, bool) or not isinstance(vary_mask, (int, np.integer)) or not 0 <= int(vary_mask) < (1 << 32):
+        raise ValueError("bm25_topk_postings: vary_mask must be an unsigned 32-bit integer, got %r" % (vary_mask,))
+    dev = db_t.device
+    if any(t.device != dev for t in (post_ids, post_rows, n_sorted, qry_ids, qry_idf, ctx_indices, ctx_row)) or \
+            (header is not None and header.device != dev):
+        raise ValueError("bm25_topk_postings: the tensors sit on different devices")
+    form, n_rows = _pool_form(header, False, n_rows, capacity)
+    out = (torch.empty((Q, K), dtype=torch.float64, device=dev), torch.empty((Q, K), dtype=torch.int64, device=dev),
+           torch.empty((Q,), dtype=torch.int64, device=dev))
+    lib.call("rat_bm25_topk_postings", _p(db_t), form, _p(header), n_rows, capacity, _p(post_ids), _p(post_rows), _p(n_sorted),
+             _p(qry_ids), _p(qry_idf), int(vary_mask), _p(ctx_indices), _p(ctx_row), R, *[_p(t) for t in out], Q, F, K, _stream(db_t))
+    return out
